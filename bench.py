@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the SyncFusion denoising hot path on MI355X (driver contract: see the task brief).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the JSON line; `roofline`, `cpu_baseline` and `extra` are null.
+`--full` measures them as well, after the headline loop.
+`--dump-outputs DIR` writes the final sample the timed call returned to DIR/sample.npy (float32, at most 64 MB); the
+inputs are seeded, so two builds given the same arguments can be compared output for output.
 
 Workload (BASELINE.json configs[1]): batch 8 clips per GPU, 2 s @ 22.05 kHz -> L0 = 45056 (= 44 * 1024, the
 nearest legal U-Net length >= 44100; SURVEY.md finding 4), bf16, embedding_scale 1.0 (one U-Net evaluation per
@@ -16,7 +21,7 @@ ranks.  value = N * K / t  (batch-steps per second summed over the N independent
 `python -m torch.distributed.run` BEFORE touching the GPU and relays rank 0's JSON line.  Under the driver's own
 torchrun launch (WORLD_SIZE set) it is a rank; a WORLD_SIZE that disagrees with --gpus is an error.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (`--full` only):
   roofline      the dominant kernel (largest share of a step's device time).  `achieved` = the ALGORITHMIC bytes (or
                 FLOPs) of its launches in one evaluation / their summed durations, measured with HIP events recorded
                 on the launch stream around every kernel of an instrumented evaluation in this process.  The whole-step
@@ -62,12 +67,16 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32", "fp32x"])
     ap.add_argument("--scale", type=float, default=1.0, help="embedding_scale (!= 1 -> classifier-free guidance, 2 evals/step)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop, also measure the `roofline`, `cpu_baseline` and `extra` objects (off: they are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final sample of the timed sample() call to DIR/sample.npy (float32)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the cpu_baseline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline object")
     ap.add_argument("--no-config0", action="store_true", help="skip cpu_baseline.config0_full (the oracle's whole 10-step guided sample)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads of the `extra` object")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the secondary workloads of the `extra` object")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--dump-launches", default=None, help="write the per-launch event timings of one evaluation to this file")
+    ap.add_argument("--dump-launches", default=None, help="write the per-launch event timings of one evaluation to this file (--full)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even with one rank: exercises the N > 1 code path on a 1-GPU box")
     ap.add_argument("--master-port", type=int, default=29533)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -75,7 +84,12 @@ def parse_args(argv=None):
     ap.add_argument("--share-gpu", action="store_true",
                     help="map every local rank onto the visible GPUs round-robin (LOCAL_RANK %% device_count): the whole N-rank launcher -> "
                          "broadcast -> timed loop -> gather -> JSON path on a 1-GPU box.  Throughput of such a run is meaningless.")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches needs --full (the instrumented evaluation belongs to the roofline object)")
+    return args
 
 
 def spawn_ranks(args, script: str = os.path.abspath(__file__), argv=None) -> int:
@@ -589,92 +603,34 @@ def extra_workloads(model, device, args, noise, channels, emb) -> dict:
     return out
 
 
-def main() -> int:
-    args = parse_args()
-    have_env = "WORLD_SIZE" in os.environ
-    if args.gpus > 1 and not have_env:
-        return spawn_ranks(args)            # before `import torch` touches the GPU: the parent stays a plain launcher
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if have_env and world != args.gpus:
-        print(f"bench.py: --gpus {args.gpus} disagrees with WORLD_SIZE={world}", file=sys.stderr)
-        return 2
+DUMP_MAX_BYTES = 60_000_000     # --dump-outputs stays under 64 MB (either unit), .npy header included
 
+
+def dump_outputs(path: str, sample) -> None:
+    """--dump-outputs: the final sample of the timed sample() call (every rank's clips, gathered) as float32 DIR/sample.npy.  Past
+    DUMP_MAX_BYTES a fixed seeded subset of whole clips is written instead, in clip order."""
+    import numpy as np
     import torch
 
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    dist_on = world > 1 or args.force_dist
-    if dist_on:
-        import torch.distributed as dist
+    x = sample.detach().float().cpu()
+    clip_bytes = 4 * x[0].numel()
+    if x.shape[0] * clip_bytes > DUMP_MAX_BYTES:
+        keep = max(1, DUMP_MAX_BYTES // clip_bytes)
+        x = x[torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "sample.npy"), x.numpy())
 
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", str(args.master_port))
-        if args.share_gpu:
-            local_rank %= max(torch.cuda.device_count(), 1)
-        torch.cuda.set_device(local_rank)
-        if args.dist_backend == "nccl":
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-        else:
-            dist.init_process_group("gloo", rank=rank, world_size=world)
-    device = torch.device("cuda", local_rank)
-    torch.cuda.set_device(device)
 
-    from syncfusion_amd import dist as sfd
+def full_measurements(args, model, device, noise, channels, emb, world, evals, ms_per_step, repeat_early):
+    """`--full`, rank 0, after the headline loop: the `roofline`, `cpu_baseline` and `extra` objects of the JSON line."""
+    import torch
+
     from syncfusion_amd import workmodel
 
-    sfd.FORCE_COLLECTIVES = bool(args.force_dist)
-
     B = args.batch
-    model = build_model(args.dtype, device)
-    model.model.sampler.use_graph = not args.no_graph
-    bcast_bytes = sfd.broadcast_module(model, src=0)          # RCCL broadcast of the weights, once, outside the timed loop
     net = model.model.net
 
-    # synthetic inputs, identical bits on every run: per-rank noise seed 1000 + rank (SURVEY 8d/8e)
-    noise = torch.randn(B, 1, L0, generator=torch.Generator().manual_seed(sfd.rank_seed(1000, rank))).to(device)
-    channels, emb = synthetic_conditioning(model, B, L0, device, real=False)   # "dummy cond" of configs[1]
-
-    def run(steps):
-        return model.model.sample(x_noisy=noise, num_steps=steps, channels=channels, embedding=emb, embedding_scale=args.scale)
-
-    def fence():
-        torch.cuda.synchronize(device)
-        if dist_on:
-            dist.barrier()
-            torch.cuda.synchronize(device)
-
-    if not args.no_graph:
-        run(2)                                                 # setup, untimed: instantiates the step graphs (reused by every later call)
-    if args.warmup > 0:
-        run(args.warmup)
-    fence()
-    t0 = time.perf_counter()
-    out = run(args.steps)
-    fence()
-    elapsed = time.perf_counter() - t0
-    if dist_on:
-        t = torch.tensor([elapsed], device=device if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t)
-    assert torch.isfinite(out).all()
-    gathered = sfd.gather_clips(out, B * world, dst=0)         # RCCL gather of the finished clips, once, after the loop
-    # The same loop three more times RIGHT AWAY (same engine object, same graphs, nothing else has run): what the headline has to be read
-    # against.  `config1_repeat` in `extra` does the same after the roofline / cpu_baseline legs.
-    repeat_early = None
-    if rank == 0 and world == 1 and not args.no_extra and not args.force_dist:
-        try:
-            r_, _, sp_ = timed_sample(model, device, noise, channels, emb, args.scale, args.steps, warm=0, clock=True)
-            repeat_early = dict(steps_per_s=round(r_, 2), steps_per_s_spread=sp_, timed_steps=args.steps)
-        except Exception as e:  # noqa: BLE001
-            repeat_early = {"error": f"{type(e).__name__}: {e}"[:300]}
-
-    if rank != 0:
-        if dist_on:
-            dist.destroy_process_group()
-        return 0
-
     # ---------------- roofline: per-kernel HIP-event timing of one instrumented evaluation ----------------
-    evals = 2 if args.scale != 1.0 else 1
     sigma = torch.full((B,), 0.5, device=device)
     net.engine().profile_forward(noise, sigma, channels, emb, args.scale)          # warm
     recs5 = net.engine().profile_forward(noise, sigma, channels, emb, args.scale, with_depth=True)
@@ -744,7 +700,6 @@ def main() -> int:
     # counted once per step -- independent of the engine's clip-parallel branches and of its launch structure
     work = workmodel.unet_work(dict(net.hparams), L0, B, evals, ES[args.dtype])
     t_roof = workmodel.step_roofline_ms(work, peak * 1e12, PEAK_HBM_GBS * 1e9)
-    ms_per_step = elapsed / args.steps * 1e3
     roof["step_algorithmic_tflop"] = round(work["flops"] / 1e12, 4)
     roof["step_algorithmic_gb"] = round(work["bytes"] / 1e9, 4)
     roof["step_roofline_ms"] = round(t_roof, 4)
@@ -842,6 +797,99 @@ def main() -> int:
     if not args.no_extra and world == 1 and not args.force_dist:
         extra = extra_workloads(model, device, args, noise, channels, emb)
         extra["config1_repeat_early"] = repeat_early
+    return roof, cpu, extra
+
+
+def main() -> int:
+    args = parse_args()
+    have_env = "WORLD_SIZE" in os.environ
+    if args.gpus > 1 and not have_env:
+        return spawn_ranks(args)            # before `import torch` touches the GPU: the parent stays a plain launcher
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if have_env and world != args.gpus:
+        print(f"bench.py: --gpus {args.gpus} disagrees with WORLD_SIZE={world}", file=sys.stderr)
+        return 2
+
+    import torch
+
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    dist_on = world > 1 or args.force_dist
+    if dist_on:
+        import torch.distributed as dist
+
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", str(args.master_port))
+        if args.share_gpu:
+            local_rank %= max(torch.cuda.device_count(), 1)
+        torch.cuda.set_device(local_rank)
+        if args.dist_backend == "nccl":
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
+        else:
+            dist.init_process_group("gloo", rank=rank, world_size=world)
+    device = torch.device("cuda", local_rank)
+    torch.cuda.set_device(device)
+
+    from syncfusion_amd import dist as sfd
+
+    sfd.FORCE_COLLECTIVES = bool(args.force_dist)
+
+    B = args.batch
+    model = build_model(args.dtype, device)
+    model.model.sampler.use_graph = not args.no_graph
+    bcast_bytes = sfd.broadcast_module(model, src=0)          # RCCL broadcast of the weights, once, outside the timed loop
+    net = model.model.net
+
+    # synthetic inputs, identical bits on every run: per-rank noise seed 1000 + rank (SURVEY 8d/8e)
+    noise = torch.randn(B, 1, L0, generator=torch.Generator().manual_seed(sfd.rank_seed(1000, rank))).to(device)
+    channels, emb = synthetic_conditioning(model, B, L0, device, real=False)   # "dummy cond" of configs[1]
+
+    def run(steps):
+        return model.model.sample(x_noisy=noise, num_steps=steps, channels=channels, embedding=emb, embedding_scale=args.scale)
+
+    def fence():
+        torch.cuda.synchronize(device)
+        if dist_on:
+            dist.barrier()
+            torch.cuda.synchronize(device)
+
+    if not args.no_graph:
+        run(2)                                                 # setup, untimed: instantiates the step graphs (reused by every later call)
+    if args.warmup > 0:
+        run(args.warmup)
+    fence()
+    t0 = time.perf_counter()
+    out = run(args.steps)
+    fence()
+    elapsed = time.perf_counter() - t0
+    if dist_on:
+        t = torch.tensor([elapsed], device=device if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t)
+    assert torch.isfinite(out).all()
+    gathered = sfd.gather_clips(out, B * world, dst=0)         # RCCL gather of the finished clips, once, after the loop
+    if args.dump_outputs and gathered is not None:
+        dump_outputs(args.dump_outputs, gathered)
+    # The same loop three more times RIGHT AWAY (same engine object, same graphs, nothing else has run): what the headline has to be read
+    # against.  `config1_repeat` in `extra` does the same after the roofline / cpu_baseline legs.
+    repeat_early = None
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not args.force_dist:
+        try:
+            r_, _, sp_ = timed_sample(model, device, noise, channels, emb, args.scale, args.steps, warm=0, clock=True)
+            repeat_early = dict(steps_per_s=round(r_, 2), steps_per_s_spread=sp_, timed_steps=args.steps)
+        except Exception as e:  # noqa: BLE001
+            repeat_early = {"error": f"{type(e).__name__}: {e}"[:300]}
+
+    if rank != 0:
+        if dist_on:
+            dist.destroy_process_group()
+        return 0
+
+    evals = 2 if args.scale != 1.0 else 1
+    ms_per_step = elapsed / args.steps * 1e3
+    roof = cpu = extra = None
+    if args.full:
+        roof, cpu, extra = full_measurements(args, model, device, noise, channels, emb, world, evals, ms_per_step, repeat_early)
 
     line = {
         "metric": "U-Net denoise steps/sec (batch x 2 s@22.05 kHz)",

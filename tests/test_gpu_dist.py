@@ -89,7 +89,7 @@ def test_two_rank_sharded_sample_equals_concatenated_single_runs(cuda):
 def test_bench_force_dist_runs_the_rccl_path_with_one_rank(cuda):
     """bench.py --force-dist: init_process_group("nccl") = RCCL with world size 1, flat weight broadcast, all_gather of the clips."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--master-port", "29657"], capture_output=True, text=True, timeout=850,
+                        "--full", "--no-cpu-baseline", "--master-port", "29657"], capture_output=True, text=True, timeout=850,
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -112,7 +112,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu(cuda):
             sock.bind(("127.0.0.1", 0))
             port = sock.getsockname()[1]
         return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", backend, "--steps", "3",
-                               "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--master-port", str(port)], capture_output=True, text=True,
+                               "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra", "--master-port", str(port)], capture_output=True, text=True,
                               timeout=700, env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
 
     r = run("nccl")

@@ -1,7 +1,7 @@
 """rocprofv3 PMC passes -> per-kernel HBM-side traffic per launch (profiles/*_pmc_traffic.json).
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d F -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --no-graph
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d W -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --no-graph
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d F -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --no-graph
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d W -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --no-graph
     python tools/pmc_traffic.py F/.../*_counter_collection.csv W/.../*_counter_collection.csv profiles/r1_k_pmc_traffic.json
 
 Units and corrections as /opt/skills/guides/MI355X_MICROARCH.md (HBM / rocprofv3 section) prescribes: the counters are in

@@ -8,14 +8,14 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [ "${SF_PROFILE_PRIMARY:-1}" = "1" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $O/bench_under_profiler.json 2> $O/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra > $O/bench_under_profiler.json 2> $O/stats.log
 # traffic passes WITHOUT the hosted weight prefetch: a prefetch workgroup's reads are charged to the launch that hosts it (the NEXT GEMM's
 # weights), which would triple the apparent traffic of the small-batch GEMMs; the timed runs keep the prefetch on
 export SF_NO_PREFETCH=1 SF_LIB_PATH=$R/syncfusion_amd/lib/libsyncfusion_amd_tuning.so
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 $R/bench.py --no-cpu-baseline --no-extra --steps 3 --warmup 1 --no-graph > /dev/null 2> $O/fetch.log
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -- python3 $R/bench.py --no-cpu-baseline --no-extra --steps 3 --warmup 1 --no-graph > /dev/null 2> $O/write.log
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 $R/bench.py --full --no-cpu-baseline --no-extra --steps 3 --warmup 1 --no-graph > /dev/null 2> $O/fetch.log
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -- python3 $R/bench.py --full --no-cpu-baseline --no-extra --steps 3 --warmup 1 --no-graph > /dev/null 2> $O/write.log
 unset SF_NO_PREFETCH SF_LIB_PATH
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace --output-format csv -d $O/mfma -- python3 $R/bench.py --no-cpu-baseline --no-extra --steps 3 --warmup 1 --no-graph > /dev/null 2> $O/mfma.log
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace --output-format csv -d $O/mfma -- python3 $R/bench.py --full --no-cpu-baseline --no-extra --steps 3 --warmup 1 --no-graph > /dev/null 2> $O/mfma.log
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace --output-format csv -d $O/mfma_onset -- python3 $R/tools/onset_one.py 32 bf16 3 > /dev/null 2> $O/mfma_onset.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/onset_stats -- python3 $R/tools/onset_one.py 32 bf16 5 > /dev/null 2> $O/onset_stats.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train_stats -- python3 $R/tools/train_step_bench.py > $O/train_step_under_profiler.json 2> $O/train_stats.log
@@ -26,7 +26,7 @@ cp $(ls $O/stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv
 python3 tools/pmc_traffic.py $(ls $O/fetch/*/*counter_collection.csv | head -1) $(ls $O/write/*/*counter_collection.csv | head -1) $O/pmc_traffic.json > $O/pmc_traffic.txt
 python3 tools/mfma_busy.py $O/mfma $O/pmc_mfma_by_kernel.csv > /dev/null
 python3 tools/mfma_busy.py $O/mfma_onset $O/pmc_mfma_onset_by_kernel.csv > /dev/null
-python3 bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python3 bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 fi
 cd $R
 # secondary workloads: kernel stats + matrix-core busy summaries of configs[2] (batch 32, guidance 2.0), one GPU's
