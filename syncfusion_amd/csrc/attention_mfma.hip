@@ -177,7 +177,9 @@ template <typename T> __global__ __launch_bounds__(128) void attention_mfma_kern
 //     4 keys) -- the 2-wave kernel writes the transposed image with 32 two-byte stores per thread and tile.  The accumulator-
 //     as-operand k order (element j of half h = key 16 s + 8 (j >> 2) + 4 h + (j & 3)) is two blocks of 4 consecutive keys:
 //     exactly two transposed reads per fragment.  Row pitch 192 B: the 4 rows of a block fall in 4 disjoint 16-bank ranges;
-//   * scores are kept in log2 units (q pre-scaled by log2(e) / 8): the exponential is one v_exp_f32.
+//   * q is pre-scaled by 1/sqrt(D) only (exact for D = 64: a power of two), never by log2(e): rounding log2(e) q to 16 bits moved
+//     a score of 240 by up to 2^-9 of itself (half a nat in bf16).  The fp32 scores go to log2 units inside the exponential's
+//     argument, exp2(fma(s, log2 e, -m)): still one v_exp_f32 and one VALU operation per score.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int W4 = 4;
 constexpr int LDV4 = 96;   // bf16 elements per row of the row-major V tile (192 B)
@@ -185,7 +187,8 @@ typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
 
 template <typename T> __global__ __launch_bounds__(256) void attention_mfma4_kernel(const T *__restrict__ q, int ldq, const T *__restrict__ kv, int ldkv,
-                                                              int L, int H, T *__restrict__ out, int ldo, float scale_log2e) {
+                                                              int L, int H, T *__restrict__ out, int ldo, float scale) {
+  constexpr float LOG2E = 1.4426950408889634f;
   __shared__ __attribute__((aligned(16))) T Ks[TK * LDK];
   __shared__ __attribute__((aligned(16))) T Vs[TK * LDV4];
   __shared__ __attribute__((aligned(16))) T Os[W4 * QW * LDO];
@@ -206,7 +209,7 @@ template <typename T> __global__ __launch_bounds__(256) void attention_mfma4_ker
     for (int s = 0; s < 4; ++s) {
       Vec16<T> v = ld16<T>(qp + 16 * s + 8 * fh);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) qf[s][j] = (T)((float)v.v[j] * scale_log2e);
+      for (int j = 0; j < 8; ++j) qf[s][j] = (T)((float)v.v[j] * scale);
     }
   }
   f32x16 o[2];
@@ -276,7 +279,7 @@ template <typename T> __global__ __launch_bounds__(256) void attention_mfma4_ker
 #pragma unroll
       for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[t][r]);
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float mnew = fmaxf(mrun, tmax);
+    const float mnew = fmaxf(mrun, tmax * LOG2E);   // running max in log2 units
     const float alpha = __builtin_amdgcn_exp2f(mrun - mnew);
     float psum = 0.f;
     frag pf[4];
@@ -284,7 +287,7 @@ template <typename T> __global__ __launch_bounds__(256) void attention_mfma4_ker
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float pv = __builtin_amdgcn_exp2f(st[t][r] - mnew);
+        const float pv = __builtin_amdgcn_exp2f(fmaf(st[t][r], LOG2E, -mnew));
         psum += pv;
         pf[2 * t + (r >> 3)][r & 7] = (T)pv;
       }
@@ -528,7 +531,7 @@ static hipError_t attention_mfma_go(const void *q, int ldq, const void *kv, int 
   if (!two_wave && L >= 256) {
     dim3 g4((L + W4 * QW - 1) / (W4 * QW), H, B);
     hipLaunchKernelGGL((attention_mfma4_kernel<T>), g4, dim3(256), 0, s, static_cast<const T *>(q), ldq, static_cast<const T *>(kv), ldkv, L, H,
-                       static_cast<T *>(out), ldo, 1.4426950408889634f / sqrtf((float)D));
+                       static_cast<T *>(out), ldo, 1.0f / sqrtf((float)D));
     return hipGetLastError();
   }
   dim3 grid((L + WAVES * QW - 1) / (WAVES * QW), H, B);

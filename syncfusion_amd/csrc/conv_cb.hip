@@ -41,6 +41,33 @@ template <typename T> __device__ __forceinline__ Vec16<T> buf_ld16(__amdgpu_buff
   return v;
 }
 
+// GroupNorm partials of one (clip, group) for the panel prologue are (mean, M2) pairs: pro 1, per statistics chunk of cb_reduce_gn
+// (chunk_rows rows x 2^log2cpg channels); pro 2, per 32 x 32 tile segment of the producing GEMM (the tile's rows inside the clip x 32).
+// Elements behind partial kc (pro 1) / behind the tile segment of row tile `mtile` (pro 2):
+__device__ __forceinline__ float part_count(bool tiles, int clip, int kc, int mtile, int L, int chunk_rows, int log2cpg) {
+  const int c0 = clip * L;
+  const int rows = tiles ? min((mtile + 1) * 32, c0 + L) - max(mtile * 32, c0) : min(chunk_rows, L - kc * chunk_rows);
+  return (float)(rows << (tiles ? 5 : log2cpg));
+}
+
+// Chan merge of the partials of one (clip, group): 8 consecutive lanes hold 4 each (partial sub + 8 k, live below lim).  Pooled mean
+// first, then M2 = sum (M2_k + n_k (mean_k - mean)^2): no raw sum of squares, so no cancellation at a large mean.  -> (mean, rstd)
+__device__ __forceinline__ float2 merge_parts(const float2 (&cs)[4], const float (&cn)[4], int sub, int lim, float rn, float eps) {
+  float s1 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (sub + 8 * k < lim) s1 = fmaf(cn[k], cs[k].x, s1);
+  const float mean = sum8_dpp(s1) * rn;
+  float s2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (sub + 8 * k < lim) {
+      const float d = cs[k].x - mean;
+      s2 += fmaf(cn[k] * d, d, cs[k].y);
+    }
+  return make_float2(mean, rsqrtf(sum8_dpp(s2) * rn + eps));
+}
+
 // MT = 32-row MFMA tiles per workgroup.  256 threads: wave w owns output columns [32 w, 32 w + 32) of the 128-column block.
 // PRO: the GroupNorm+SiLU panel prologue, a compile-time switch (as a run-time branch its loaded values meet "undefined" at the join
 // and the compiler's copies put a wait in front of the weight loads).
@@ -80,7 +107,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
     const bool ok = j < PR && r >= 0 && r < M;
     pv[i] = buf_ld16<T>(rS, ok ? (unsigned)r * row_b + col_b : OOB);
   }
-  // ---- 2. GroupNorm operands: gamma / beta of this thread's channel octet, chunk sums of the clips the panel touches ----------
+  // ---- 2. GroupNorm operands: gamma / beta of this thread's channel octet, chunk statistics of the clips the panel touches ----------
   //         (8 lanes per (clip, group) pair, 4 chunks each; every address is clamped so that the loads are branch-free and all in
   //         flight together, behind the panel loads and in front of the weight loads: the first wait must not cover the weights)
   const int gshift = KC_LOG2 + (KB == 2 ? 1 : 0) - a.log2cpg;   // log2(groups inside the workgroup's channel range)
@@ -90,6 +117,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   f32x4 ga[2], be[2];
   constexpr int NRD = 1;
   float2 cs[NRD][4];
+  float cn[NRD][4];   // elements behind each partial (Chan merge weights)
   int lim[NRD] = {0};
   const int sub = tid & 7;
   if constexpr (PRO) {
@@ -99,7 +127,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
       ga[q] = *reinterpret_cast<const f32x4 *>(a.gamma + cb * KCW + cv * 8 + 4 * q);
       be[q] = *reinterpret_cast<const f32x4 *>(a.beta + cb * KCW + cv * 8 + 4 * q);
     }
-    // pro 1: chunk sums [clip][nch][G]; pro 2: tile sums [m tile][C / 32][segment] of the producing GEMM (kernels.h).  One address
+    // pro 1: chunk (mean, M2) [clip][nch][G]; pro 2: tile (mean, M2) [m tile][C / 32][segment] of the producing GEMM (kernels.h).  One address
     // select per load instead of two code paths: loaded values that meet at a join cost a wait in front of the weight loads.
     const bool tiles = a.pro == 2;
     const int ltpg = a.log2cpg - 5, ct = a.C >> 5;               // log2(32-column tiles per group), tiles per row
@@ -118,6 +146,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
         const unsigned off2 = (unsigned)(((mtile * ct + tile) * 2 + (clip - divL(mtile << 5))) * 2);
         const unsigned off1 = (unsigned)((((clip * a.nch + kc) * G) + (cb << gshift) + gi) * 2);
         cs[rd][k] = *reinterpret_cast<const float2 *>(a.stats + (tiles ? off2 : off1));
+        cn[rd][k] = part_count(tiles, clip, kc, mtile, a.L, a.chunk_rows, a.log2cpg);
       }
     }
   }
@@ -143,20 +172,9 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
     const float rn = 1.0f / ((float)a.L * (float)(1 << a.log2cpg));
 #pragma unroll
     for (int rd = 0; rd < NRD; ++rd) {
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (sub + 8 * k < lim[rd]) {
-          s1 += cs[rd][k].x;
-          s2 += cs[rd][k].y;
-        }
-      s1 = sum8_dpp(s1);
-      s2 = sum8_dpp(s2);
+      const float2 st = merge_parts(cs[rd], cn[rd], sub, lim[rd], rn, a.eps);
       const int p = (tid >> 3) + 32 * rd;
-      if (sub == 0 && p < npair) {
-        const float mean = s1 * rn;
-        gstat[p >> gshift][p & ((1 << gshift) - 1)] = make_float2(mean, rsqrtf(fmaxf(fmaf(s2, rn, -mean * mean), 0.f) + a.eps));
-      }
+      if (sub == 0 && p < npair) gstat[p >> gshift][p & ((1 << gshift) - 1)] = st;
     }
     __syncthreads();
   }
@@ -265,6 +283,7 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
   const int npair = nclip << gshift;
   f32x4 ga = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
   float2 cs[4];
+  float cn[4];
   int lim = 0;
   const int sub = tid & 7;
   if constexpr (PRO) {
@@ -286,6 +305,7 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
       const unsigned off2 = (unsigned)(((mtile * ct + tile) * 2 + (clip - divL(mtile << 5))) * 2);
       const unsigned off1 = (unsigned)((((clip * a.nch + kc) * G) + (cb << gshift) + gi) * 2);
       cs[k] = *reinterpret_cast<const float2 *>(a.stats + (tiles ? off2 : off1));
+      cn[k] = part_count(tiles, clip, kc, mtile, a.L, a.chunk_rows, a.log2cpg);
     }
   }
   // ---- 3. the wave's weight slice: 24 (hi, lo') fragment pairs, 48 KB contiguous per wave, independent of the producer kernel -----------
@@ -307,20 +327,9 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
   // ---- 4. statistics of the touched (clip, group) pairs -> LDS ---------------------------------------------------------------------------
   if constexpr (PRO) {
     const float rn = 1.0f / ((float)a.L * (float)(1 << a.log2cpg));
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (sub + 8 * k < lim) {
-        s1 += cs[k].x;
-        s2 += cs[k].y;
-      }
-    s1 = sum8_dpp(s1);
-    s2 = sum8_dpp(s2);
+    const float2 st = merge_parts(cs, cn, sub, lim, rn, a.eps);
     const int p = tid >> 3;
-    if (sub == 0 && p < npair) {
-      const float mean = s1 * rn;
-      gstat[p >> gshift][p & ((1 << gshift) - 1)] = make_float2(mean, rsqrtf(fmaxf(fmaf(s2, rn, -mean * mean), 0.f) + a.eps));
-    }
+    if (sub == 0 && p < npair) gstat[p >> gshift][p & ((1 << gshift) - 1)] = st;
     __syncthreads();
   }
   // ---- 5. panel -> LDS: GroupNorm + SiLU in fp32, then split into the two fp16 images ----------------------------------------------------
@@ -437,13 +446,15 @@ __global__ void pack_conv_cb_kernel(const float *__restrict__ w, int N, int C, T
   }
 }
 
-// slabs -> h = sum + bias (16-bit) and GroupNorm chunk sums (sum, sum of squares per (clip, chunk, group)) of the STORED h.  Workgroup = (clip, chunk of 8 P rows, 128-column block);
-// thread = 4 consecutive columns of one row per pass.
+// slabs -> h = sum + bias (16-bit) and GroupNorm chunk statistics (mean, M2 per (clip, chunk, group)) of the STORED h, in two passes over the
+// values the threads keep in registers (raw sums of squares cancel once a group's mean is large next to its spread).  Workgroup = (clip,
+// chunk of 8 P rows, 128-column block); thread = 4 consecutive columns of one row per pass.
 template <typename T, int S, int P>
 __global__ __launch_bounds__(256) void cb_reduce_gn_kernel(const float *__restrict__ slab, const int M, const int N, const int L,
                                                            const float *__restrict__ bias, T *__restrict__ out, const int out_ld, const int G,
                                                            float *__restrict__ stats, const int nch, const int nreal, const Prefetch pf) {
   __shared__ float red[4][8][2];
+  __shared__ float gmean[8];
   if ((int)blockIdx.x >= nreal) {
     prefetch_slice(pf, (int)blockIdx.x - nreal, 256);
     return;
@@ -464,7 +475,8 @@ __global__ __launch_bounds__(256) void cb_reduce_gn_kernel(const float *__restri
     for (int s = 0; s < S; ++s) v[p][s] = *reinterpret_cast<const f32x4 *>(slab + ((size_t)s * M + m) * N + c);
   }
   const f32x4 bi = *reinterpret_cast<const f32x4 *>(bias + c);
-  float s1 = 0.f, s2 = 0.f;
+  float xs[P][4];   // the stored values (rows past the chunk: 0, and left out of both passes)
+  float s1 = 0.f;
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     const int lr = p * 8 + rr;
@@ -472,41 +484,50 @@ __global__ __launch_bounds__(256) void cb_reduce_gn_kernel(const float *__restri
 #pragma unroll
     for (int s = 1; s < S; ++s) x += v[p][s];   // fixed order: deterministic
     x += bi;
-    if (lr < rows) {
-      T o[4];
+    T o[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[e] = from_f<T>(x[e]);
-        const float xo = to_f(o[e]);
-        s1 += xo;
-        s2 = fmaf(xo, xo, s2);
-      }
-      __builtin_memcpy(__builtin_assume_aligned(out + ((size_t)b * L + l0 + lr) * out_ld + c, 4 * sizeof(T)), o, 4 * sizeof(T));
+    for (int e = 0; e < 4; ++e) {
+      o[e] = from_f<T>(x[e]);
+      xs[p][e] = lr < rows ? to_f(o[e]) : 0.f;
+      s1 += xs[p][e];
     }
+    if (lr < rows) __builtin_memcpy(__builtin_assume_aligned(out + ((size_t)b * L + l0 + lr) * out_ld + c, 4 * sizeof(T)), o, 4 * sizeof(T));
   }
-  // group totals: lanes of one group are `span` consecutive channel quads; lane ^ 32 is the same quad one row further
+  // group totals: lanes of one group are `span` consecutive channel quads; lane ^ 32 is the same quad one row further.  Fixed shapes: deterministic
   const int cpg = N / G, span = cpg / 4;   // 4 .. 32
-  for (int off = 1; off < span; off <<= 1) {
-    s1 += __shfl_xor(s1, off, 64);
-    s2 += __shfl_xor(s2, off, 64);
-  }
-  s1 += __shfl_xor(s1, 32, 64);
-  s2 += __shfl_xor(s2, 32, 64);
   const int gpb = 128 / cpg;
-  if (lane < 32 && (cq % span) == 0) {
-    red[wave][cq / span][0] = s1;
-    red[wave][cq / span][1] = s2;
-  }
-  __syncthreads();
-  if (tid < gpb) {
-    float a1 = 0.f, a2 = 0.f;
+  auto group_total = [&](float t, int k) {
+    for (int off = 1; off < span; off <<= 1) t += __shfl_xor(t, off, 64);
+    t += __shfl_xor(t, 32, 64);
+    if (lane < 32 && (cq % span) == 0) red[wave][cq / span][k] = t;
+    __syncthreads();
+    float a = 0.f;
+    if (tid < gpb) {
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      a1 += red[w][tid][0];
-      a2 += red[w][tid][1];
+      for (int w = 0; w < 4; ++w) a += red[w][tid][k];
     }
-    float *o = stats + (((size_t)b * nch + ch) * G + cblk * gpb + tid) * 2;   // (sum, sum of squares): the consumer just adds the chunks
-    o[0] = a1;
+    return a;
+  };
+  // pass 1: the chunk's group means
+  const float a1 = group_total(s1, 0);
+  if (tid < gpb) gmean[tid] = a1 / ((float)rows * (float)cpg);
+  __syncthreads();
+  // pass 2: squares about them
+  const float mu = gmean[cq / span];
+  float s2 = 0.f;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const bool live = p * 8 + rr < rows;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = live ? xs[p][e] - mu : 0.f;
+      s2 = fmaf(d, d, s2);
+    }
+  }
+  const float a2 = group_total(s2, 1);
+  if (tid < gpb) {
+    float *o = stats + (((size_t)b * nch + ch) * G + cblk * gpb + tid) * 2;   // (mean, M2) of the chunk: the consumer merges the chunks (Chan)
+    o[0] = gmean[tid];
     o[1] = a2;
   }
 }
@@ -604,7 +625,7 @@ bool conv_cb_shape_ok(int dt, int B, int L, int C, int N, int G) {
   return true;
 }
 
-// pro 2 (GroupNorm sums per 32 x 32 tile of the producing GEMM): a group must be whole tiles, a (clip, group) at most 32 of them
+// pro 2 (GroupNorm statistics per 32 x 32 tile of the producing GEMM): a group must be whole tiles, a (clip, group) at most 32 of them
 bool conv_cb_tile_stats_ok(int L, int C, int G) {
   if (G < 1 || C % G) return false;
   const int cpg = C / G;

@@ -259,22 +259,35 @@ __global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const ConvGemmArgs a,
     q = sum8_dpp(q);
     if (nq == 0 && live) *reinterpret_cast<float2 *>(a.rowpart_out + ((size_t)em * a.rowpart_nt + nt) * 2) = make_float2(mean, q);
   }
-  if (a.gnpart_out) {   // GroupNorm tile sums of the stored values for the channel-block convolution that follows (kernels.h)
-    const float s1 = sum8_dpp((xo[0] + xo[1]) + (xo[2] + xo[3]));
-    const float s2 = sum8_dpp(fmaf(xo[0], xo[0], xo[1] * xo[1]) + fmaf(xo[2], xo[2], xo[3] * xo[3]));
+  if (a.gnpart_out) {   // GroupNorm tile statistics of the stored values for the channel-block convolution that follows (kernels.h)
+    const float mean = sum8_dpp((xo[0] + xo[1]) + (xo[2] + xo[3])) * (1.0f / 32.0f);   // (mean, M2) of the row's 32 stored values
+    float q = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = xo[e] - mean;
+      q = fmaf(d, d, q);
+    }
+    q = sum8_dpp(q);
     if (nq == 0) {
-      gsum[2 * ml] = live ? s1 : 0.f;
-      gsum[2 * ml + 1] = live ? s2 : 0.f;
+      gsum[2 * ml] = mean;
+      gsum[2 * ml + 1] = q;
     }
     __syncthreads();
     if (tid < 2) {   // segment 0: rows of the first row's clip; segment 1: rows of the next clip
       const int rbnd = min((m0 / a.Lout + 1) * a.Lout - m0, 32);
-      const int lo = tid == 0 ? 0 : rbnd, hi = tid == 0 ? rbnd : 32;
+      const int lo = tid == 0 ? 0 : rbnd, hi = tid == 0 ? rbnd : min(32, a.M - m0);   // rows past M belong to no clip
+      // the segment's (mean, M2) from its rows' (32 values each, row order), in one pass about the first row's mean p:
+      // d_r = mean_r - p,  mean = p + sum d / k,  M2 = sum (M2_r + 32 d_r^2) - 32 (sum d)^2 / k.  (0, 0) when empty
+      const float p = hi > lo ? gsum[2 * lo] : 0.f;
       float t1 = 0.f, t2 = 0.f;
       for (int r = lo; r < hi; ++r) {
-        t1 += gsum[2 * r];
-        t2 += gsum[2 * r + 1];
+        const float d = gsum[2 * r] - p;
+        t1 += d;
+        t2 += fmaf(32.f * d, d, gsum[2 * r + 1]);
       }
+      const float dk = hi > lo ? t1 / (float)(hi - lo) : 0.f;
+      t2 = fmaxf(fmaf(-32.f * t1, dk, t2), 0.f);
+      t1 = p + dk;
       *reinterpret_cast<float2 *>(a.gnpart_out + (((size_t)mt * ntiles + nt) * 2 + tid) * 2) = make_float2(t1, t2);
     }
   }

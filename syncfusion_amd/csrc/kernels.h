@@ -95,7 +95,7 @@ struct ConvGemmArgs {
   int rowpart_nt = 0;
   // GroupNorm partials of the STORED output for the channel-block convolution that consumes it (conv_gemm_wp, 32x32 tiles, 1-D,
   // Lout >= 32 so that a tile touches at most two clips): gnpart_out[((m_tile * (n_store / 32) + n_tile) * 2 + seg) * 2 + {0,1}] =
-  // (sum, sum of squares) over the tile's rows of the clip of its first row (seg 0) and of the next clip (seg 1).
+  // (mean, M2) over the tile's rows of the clip of its first row (seg 0) and of the next clip (seg 1); (0, 0) for an empty segment.
   float *gnpart_out = nullptr;
   //     ln_colsum != nullptr (plain normalisation, no second source): the source is multiplied RAW and the LayerNorm is
   //     applied to the accumulator instead,  rstd_m * (acc[m][n] - mean_m * ln_colsum[n]),  ln_colsum[n] = sum_k w[n][k].
@@ -214,10 +214,10 @@ hipError_t launch_d0_tail(int dt, const ThinTailArgs &a, hipStream_t s);
 // ---------------------------------------------------------------------------------------
 // Channel-block split-K convolution for the deep levels at small batch (conv_cb.hip): k = 3, stride 1, padding 1, 16-bit types.
 //   slab[cb][m][n] = sum_{tap, c in block cb} W[n][c][tap] * pro(src)[m + tap - 1][c]      (fp32, no bias; cb = 0 .. C / 128 - 1)
-//   pro 1: SiLU(GroupNorm(src)) from the chunk sums stats [B][nch][G][2] = (sum, sum of squares) that cb_reduce_gn leaves
-//          (nch <= 32 chunks per clip), applied while the (rows + 2) x 128 activation panel is staged in LDS
-//   pro 2: the same from the TILE sums the producing GEMM's epilogue leaves (ConvGemmArgs::gnpart_out: per 32-row x 32-column
-//          tile and clip segment); needs C / G >= 32 and at most 32 tiles per (clip, group)
+//   pro 1: SiLU(GroupNorm(src)) from the chunk statistics [B][nch][G][2] = (mean, M2) that cb_reduce_gn leaves (nch <= 32 chunks
+//          of chunk_rows rows per clip, merged with Chan's formula), applied while the (rows + 2) x 128 activation panel is staged in LDS
+//   pro 2: the same from the TILE statistics the producing GEMM's epilogue leaves (ConvGemmArgs::gnpart_out: (mean, M2) per 32-row x
+//          32-column tile and clip segment); needs C / G >= 32 and at most 32 tiles per (clip, group)
 // The launches that follow sum the slabs: cb_reduce_gn (+ bias -> 16-bit h and its GroupNorm chunk partials) and cb_reduce_ln
 // (+ bias + residual, LayerNorm over the row, Modulation -> 16-bit m).
 // ---------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 // Normalisation kernels (channels-last):
 //   gn_stats     GroupNorm partial statistics  (mean, M2) per (clip, row-chunk, group); the consumer
-//                convolution merges the chunks (Chan) in its prologue -- deterministic, no atomics.
+//                convolution merges the chunks (Chan) in its prologue -- deterministic, no atomics.  The sums
+//                are taken about a pivot (the chunk's first value of the group): the one-pass M2 of raw sums
+//                cancels catastrophically once a group's mean is large next to its spread.
 //   ln_modulate  per-row LayerNorm over C fused with the a-unet Modulation  y = xhat*(1+s[b]) + t[b]
 // Both are pure streaming kernels (HBM/L2-bound): 16-byte loads, wave shuffles, one pass.
 #include <cstdlib>
@@ -54,21 +56,25 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T *__restrict__ x, 
   float s[V], q[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) s[j] = q[j] = 0.f;
+  const int cpg = C / G;
 
   if (vpr <= 256) {
     const int cv = tid % vpr;                // fixed column set of this thread
     const int rstep = 256 / vpr;
+    float pv[V];                             // pivot of each column's group: its value at (row r0, first channel of the group)
+#pragma unroll
+    for (int j = 0; j < V; ++j) pv[j] = to_f(base[((cv * V + j) / cpg) * cpg]);
     for (int r = tid / vpr; r < rows; r += rstep) {
       const T *p = base + (size_t)r * ld + cv * V;
       if constexpr (V == 1) {
-        float v = to_f(p[0]);
+        float v = to_f(p[0]) - pv[0];
         s[0] += v;
         q[0] = fmaf(v, v, q[0]);
       } else {
         Vec16<T> v = ld16<T>(p);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-          float f = v.get(j);
+          float f = v.get(j) - pv[j];
           s[j] += f;
           q[j] = fmaf(f, f, q[j]);
         }
@@ -82,7 +88,6 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T *__restrict__ x, 
     }
     __syncthreads();
     const int slots = 256 / vpr;
-    const int cpg = C / G;
     if ((G & (G - 1)) == 0 && G <= 256) {
       // 256/G threads per group: strided partial sums, then a fixed-shape LDS tree (deterministic)
       const int tpg = 256 / G, g = tid / tpg, j = tid - g * tpg;
@@ -104,13 +109,13 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T *__restrict__ x, 
         }
         __syncthreads();
       }
-      if (j == 0) {
+      if (j == 0) {   // shifted sums: M2 = sum d^2 - (sum d)^2 / n with d = x - pivot, mean = pivot + sum d / n
         const float a = part_s[tid], q2 = part_q[tid];
         const float n = (float)rows * (float)cpg;
-        const float mean = a / n;
+        const float md = a / n;
         float *o = slab + (((size_t)b * nch + ch) * G + g) * 2;
-        o[0] = mean;
-        o[1] = fmaxf(q2 - a * mean, 0.f);
+        o[0] = to_f(base[g * cpg]) + md;
+        o[1] = fmaxf(q2 - a * md, 0.f);
       }
     } else if (tid < G) {
       float ts = 0.f, tq = 0.f;
@@ -120,18 +125,18 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T *__restrict__ x, 
           tq += part_q[sl * C + c];
         }
       float n = (float)rows * (float)cpg;
-      float mean = ts / n;
-      float m2 = fmaxf(tq - ts * mean, 0.f);
+      float md = ts / n;
+      float m2 = fmaxf(tq - ts * md, 0.f);
       float *o = slab + (((size_t)b * nch + ch) * G + tid) * 2;
-      o[0] = mean;
+      o[0] = to_f(base[tid * cpg]) + md;
       o[1] = m2;
     }
   } else {
     // wide rows (C/V > 256): every thread walks several column sets; group of a column set is uniform
     // per access because cpg >= V here.  Accumulate per group through LDS in a fixed order.
-    const int cpg = C / G;
     for (int g = 0; g < G; ++g) {
       float ts = 0.f, tq = 0.f;
+      const float pivot = to_f(base[g * cpg]);
       const int v0 = g * cpg / V, v1 = (g + 1) * cpg / V;
       const int nv = v1 - v0;
       for (int i = tid; i < rows * nv; i += 256) {
@@ -139,7 +144,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T *__restrict__ x, 
         Vec16<T> v = ld16<T>(base + (size_t)r * ld + cv * V);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-          float f = v.get(j);
+          float f = v.get(j) - pivot;
           ts += f;
           tq = fmaf(f, f, tq);
         }
@@ -154,10 +159,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T *__restrict__ x, 
           c += part_q[t];
         }
         float n = (float)rows * (float)cpg;
-        float mean = a / n;
+        float md = a / n;
         float *o = slab + (((size_t)b * nch + ch) * G + g) * 2;
-        o[0] = mean;
-        o[1] = fmaxf(c - a * mean, 0.f);
+        o[0] = pivot + md;
+        o[1] = fmaxf(c - a * md, 0.f);
       }
       __syncthreads();
     }
@@ -198,12 +203,14 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const T *__restrict__ 
         sh[i][q] = *reinterpret_cast<const f32x4 *>(ss + (size_t)b * ss_ld + C + c0);
       }
   }
+  // pivot: the row's first value (element 0 of the row's first lane; tpr divides 64): the mean of a constant row comes out exact
+  const float pivot = __shfl(v[0].get(0), (tid & 63) - sub, 64);
 #pragma unroll
   for (int i = 0; i < VPT; ++i)
 #pragma unroll
-    for (int j = 0; j < V; ++j) sum += v[i].get(j);
+    for (int j = 0; j < V; ++j) sum += v[i].get(j) - pivot;
   for (int o = tpr >> 1; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  const float mean = sum / (float)C;
+  const float mean = pivot + sum / (float)C;
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < VPT; ++i)
@@ -348,18 +355,23 @@ __global__ __launch_bounds__(512) void gn_silu_reg_kernel(const T *__restrict__ 
     v[i] = on ? ld16<T>(base + (size_t)rr[i] * ld + cv * V) : zero16<T>();
   }
   const float n = (float)L * (float)cpg;
+  // pass 1 about a pivot (the slab's first value): the mean of an (offset or constant) group comes out as pivot + a small
+  // correction, exact for a constant group -- a raw sum / n is off by its rounding, which 1 / sqrt(eps) then amplifies
+  const float pivot = to_f(base[0]);
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < RV; ++i)
+    if (tid + i * 512 < nv) {
 #pragma unroll
-    for (int j = 0; j < V; ++j) s += v[i].get(j);   // padding vectors are zero
+      for (int j = 0; j < V; ++j) s += v[i].get(j) - pivot;
+    }
   s = wave_sum_dpp(s);
   if ((tid & 63) == 0) red[0][wave] = s;
   __syncthreads();
   float tot = 0.f;
 #pragma unroll
   for (int w = 0; w < 8; ++w) tot += red[0][w];
-  const float mean = tot / n;
+  const float mean = pivot + tot / n;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < RV; ++i) {
@@ -378,18 +390,18 @@ __global__ __launch_bounds__(512) void gn_silu_reg_kernel(const T *__restrict__ 
 #pragma unroll
   for (int w = 0; w < 8; ++w) tq += red[1][w];
   const float rstd = rsqrtf(tq / n + eps);
-  float sc[V], sh[V];   // y = x * sc + sh
+  float sc[V], sh[V];   // y = (x - mean) * sc + sh: centred first (x * sc + (beta - mean * sc) rounds mean * sc, |mean| rstd ~ mean/std)
 #pragma unroll
   for (int j = 0; j < V; ++j) {
     sc[j] = rstd * ga[j >> 2][j & 3];
-    sh[j] = fmaf(-mean, sc[j], be[j >> 2][j & 3]);
+    sh[j] = be[j >> 2][j & 3];
   }
 #pragma unroll
   for (int i = 0; i < RV; ++i) {
     if (tid + i * 512 < nv) {
       Vec16<T> o;
 #pragma unroll
-      for (int j = 0; j < V; ++j) o.set(j, silu_t<FAST>(fmaf(v[i].get(j), sc[j], sh[j])));
+      for (int j = 0; j < V; ++j) o.set(j, silu_t<FAST>(fmaf(v[i].get(j) - mean, sc[j], sh[j])));
       if constexpr (sizeof(T) == 4) {
         if (xfmt) {
           st4_x3(out + ((size_t)b * L + rr[i]) * out_ld, g * cpg + cv * V, o.v);
@@ -417,8 +429,11 @@ __global__ __launch_bounds__(256) void gn_silu_apply_kernel(const T *__restrict_
   const int cpg = C / G;
   for (int g = tid; g < G; g += 256) {
     const float *sb = slab + ((size_t)b * nch * G + g) * 2;
-    float n = 0.f, mean = 0.f, m2 = 0.f;
-    for (int ch0 = 0; ch0 < nch; ch0 += 8) {   // eight chunk partials per memory round trip, merged in chunk order (same bits as one at a time)
+    // Chan merge about the first chunk's mean m0: the running sums hold n_k (mean_k - m0), small next to an offset mean, and the
+    // mean is rounded once at the end (a running mean of an offset group collects one rounding of its full size per chunk)
+    const float m0 = sb[0];
+    float n = 0.f, s = 0.f, m2 = 0.f;
+    for (int ch0 = 0; ch0 < nch; ch0 += 8) {   // eight chunk partials per memory round trip, merged in chunk order
       float2 v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] = ch0 + u < nch ? *reinterpret_cast<const float2 *>(sb + (size_t)(ch0 + u) * G * 2) : make_float2(0.f, 0.f);
@@ -427,24 +442,26 @@ __global__ __launch_bounds__(256) void gn_silu_apply_kernel(const T *__restrict_
         const int ch = ch0 + u;
         if (ch < nch) {
           const float nb = (float)min(chunk_rows, L - ch * chunk_rows) * (float)cpg;
-          const float delta = v[u].x - mean, tot = n + nb;
-          mean += delta * (nb / tot);
-          m2 += v[u].y + delta * delta * (n * nb / tot);
-          n = tot;
+          const float d = v[u].x - m0;
+          s = fmaf(nb, d, s);
+          m2 += fmaf(nb * d, d, v[u].y);
+          n += nb;
         }
       }
     }
-    mean_s[g] = mean;
-    rstd_s[g] = rsqrtf(m2 / n + eps);
+    const float dm = s / n;   // M2 about the pooled mean: sum (M2_k + n_k d_k^2) - n dm^2, all terms about m0
+    mean_s[g] = m0 + dm;
+    rstd_s[g] = rsqrtf(fmaxf(m2 - n * dm * dm, 0.f) / n + eps);
   }
   __syncthreads();
   const int vpr = C / V, cv = tid % vpr, rstep = 256 / vpr;
-  float sc[V], sh[V];
+  float mu[V], sc[V], sh[V];   // y = (x - mean) * sc + beta: centred first, as in the kernels above
 #pragma unroll
   for (int j = 0; j < V; ++j) {
     const int c = cv * V + j, g = c / cpg;
+    mu[j] = mean_s[g];
     sc[j] = rstd_s[g] * gamma[c];
-    sh[j] = fmaf(-mean_s[g], sc[j], beta[c]);
+    sh[j] = beta[c];
   }
   const int r0 = blockIdx.x * rows_per_wg, r1 = min(L, r0 + rows_per_wg);
   const T *xb = x + ((size_t)b * L) * ld + cv * V;
@@ -454,7 +471,7 @@ __global__ __launch_bounds__(256) void gn_silu_apply_kernel(const T *__restrict_
     const Vec16<T> v = ld16<T>(xb + (size_t)r * ld);
     Vec16<T> o;
 #pragma unroll
-    for (int j = 0; j < V; ++j) o.set(j, silu_t<FAST>(fmaf(v.get(j), sc[j], sh[j])));
+    for (int j = 0; j < V; ++j) o.set(j, silu_t<FAST>(fmaf(v.get(j) - mu[j], sc[j], sh[j])));
     if constexpr (sizeof(T) == 4) {
       if (xfmt) {
         st4_x3(out + ((size_t)b * L + r) * out_ld, cv * V, o.v);

@@ -72,7 +72,7 @@ struct Plan {  // everything carved out of the caller's workspace for one (B, L0
   int64_t rowpart_half = 0, rowpart_stride = 0;
   float *cbslab = nullptr;     // fp32 partial slabs of the channel-block convolutions: one buffer per branch
   int64_t cbslab_stride = 0;
-  float *gnpart = nullptr;     // GroupNorm tile sums a producing GEMM leaves for the next item's first convolution: one buffer per branch
+  float *gnpart = nullptr;     // GroupNorm tile statistics a producing GEMM leaves for the next item's first convolution: one buffer per branch
   int64_t gnpart_stride = 0;
   // modulation vectors: per clip ([Bt][mod_ld], mod_stride = mod_ld) for a single forward, or ONE row shared by all
   // clips (mod_stride = 0) inside the sampler, where sigma is the same for every clip and the rows of all steps are
@@ -758,8 +758,8 @@ struct Exec {
   Plan &p;
   hipStream_t s;
   const void *stats_of = nullptr;   // thin levels: the activation whose GroupNorm partials currently sit in p.slab
-  const void *gnpart_of = nullptr;  // channel-block levels: the activation whose GroupNorm tile sums currently sit in p.gnpart
-  bool up_gnpart = false;           // block(d + 1) left the tile sums of its output (level d's next item input) in p.gnpart
+  const void *gnpart_of = nullptr;  // channel-block levels: the activation whose GroupNorm tile statistics currently sit in p.gnpart
+  bool up_gnpart = false;           // block(d + 1) left the tile statistics of its output (level d's next item input) in p.gnpart
   int cur_depth = -1;               // depth tag of the launches being issued (profile records, roofline.depth_groups)
 
   template <class F> void timed(const char *label, double flops, double bytes, F &&f) {
@@ -832,7 +832,7 @@ struct Exec {
     return pf;
   }
 
-  // the producer of an item input of level d should leave GroupNorm tile sums (ConvGemmArgs::gnpart_out) for conv_cb's prologue
+  // the producer of an item input of level d should leave GroupNorm tile statistics (ConvGemmArgs::gnpart_out) for conv_cb's prologue
   bool wants_gnpart(int d) const {
     static const bool off = tune_env("SF_NO_CB_TILESTATS") != nullptr;   // A/B aid: keep the gn_silu launch in front of conv1
     if (off || d < 0 || d >= (int)p.lv.size()) return false;
@@ -1072,7 +1072,7 @@ struct Exec {
       a.eps = 1e-5f;
       a.pf = pf_cb(g.conv2, cwgs);
       if (gnpart_of == cur && wants_gnpart(d)) {
-        // the GEMM that produced `cur` left its GroupNorm tile sums: GroupNorm+SiLU rides in conv1's panel prologue, no gn_silu launch
+        // the GEMM that produced `cur` left its GroupNorm tile statistics: GroupNorm+SiLU rides in conv1's panel prologue, no gn_silu launch
         a.src = cur;
         a.pro = 2;
         a.stats = p.gnpart;
