@@ -368,6 +368,45 @@ int sf_op_ln_modulate(int dtype, const void *x, const float *scale_shift /* (B, 
 /* multi-head attention on packed projections: q:(B,L,H*D), kv:(B,L,2*H*D) -> out:(B,L,H*D) */
 int sf_op_attention(int dtype, const void *q, const void *kv, int B, int L, int heads, int head_dim, void *out, void *stream);
 
+
+/* ---- VideoOnsetNet training (fp32; main/module_onset.py trains main/onset_net.py:46-63 in fp32) ----------------------------------------
+ * Video activations are channels-last rows: x row ((n*T + t)*Hi + hi)*Wi + wi with cin_ld columns, y row ((n*T + t)*Ho + ho)*Wo + wo with cout_ld
+ * columns; columns past the real channel count hold zeros (inputs must, outputs are written so).  Weights and their gradients are PyTorch's
+ * Conv3d layout (cout, cin, kt, kh, kw), fp32, no bias.  Temporal stride 1, 2 pt == kt - 1; Ho = (Hi + 2 ph - kh) / sh + 1 (likewise Wo).
+ * Needs cin_ld % 4 == 0, cout_ld % 8 == 0.  ws >= sf_op_vconv_workspace_bytes(desc) (the same bound for the forward and backward calls).
+ * sf_op_vconv_bwd: dx (input rows, cin_ld columns) and / or dw (either may be NULL); the data gradient supports stride-1 'same' convolutions and
+ * (1, kh, kw) kernels of any spatial stride.  No atomics: the results are bit-reproducible. */
+typedef struct {
+  int32_t N, T, Hi, Wi;      /* clips, frames per clip, input frame size */
+  int32_t cin, cin_ld;       /* input channels, input row length (floats) */
+  int32_t cout, cout_ld;     /* output channels, output row length (floats) */
+  int32_t kt, kh, kw;        /* kernel */
+  int32_t sh, sw;            /* spatial stride */
+  int32_t pt, ph, pw;        /* zero padding */
+} sf_vconv_desc;
+int64_t sf_op_vconv_workspace_bytes(const sf_vconv_desc *desc /* host */);
+int sf_op_vconv_fwd(const sf_vconv_desc *desc, const float *x, const float *w, float *y, void *ws, int64_t ws_bytes, void *stream);
+int sf_op_vconv_bwd(const sf_vconv_desc *desc, const float *x, const float *w, const float *dy, float *dx, float *dw, void *ws, int64_t ws_bytes,
+                    void *stream);
+/* BatchNorm3d in train mode over channels-last rows (rows, ld), C real channels (rows >= 2, ld % 4 == 0):
+ *   y = act(xhat * gamma + beta + res),  xhat = (x - mean) / sqrt(var + eps),  mean / var (biased) over all rows;  res (rows, ld) or NULL,
+ *   act = ReLU when relu != 0.  save_mean / save_invstd (C): mean and 1 / sqrt(var + eps) for the backward call.  running_mean / running_var
+ *   (C, or NULL) <- (1 - momentum) * running + momentum * (mean | var * rows / (rows - 1));  *num_batches_tracked (int64, or NULL) += 1.
+ * sf_op_bn_train_bwd: dy = the gradient of y;  y = the forward output when relu was on (its mask), else NULL;  dx = gamma * invstd *
+ *   (dz - mean(dz) - xhat * mean(dz * xhat)) with dz = dy masked;  dres (or NULL) = dz, the residual's gradient;  dgamma / dbeta (C, or NULL).
+ *   Per-channel sums are taken per row slice and merged in a fixed order (deterministic).  ws >= sf_op_bn_train_workspace_bytes. */
+int64_t sf_op_bn_train_workspace_bytes(int64_t rows, int C);
+int sf_op_bn_train_fwd(const float *x, const float *res, int64_t rows, int C, int ld, const float *gamma, const float *beta, float eps, float momentum,
+                       float *running_mean, float *running_var, int64_t *num_batches_tracked, int relu, float *y, float *save_mean, float *save_invstd,
+                       void *ws, int64_t ws_bytes, void *stream);
+int sf_op_bn_train_bwd(const float *x, const float *y, const float *dy, int64_t rows, int C, int ld, const float *gamma, const float *save_mean,
+                       const float *save_invstd, float *dx, float *dres, float *dgamma, float *dbeta, void *ws, int64_t ws_bytes, void *stream);
+/* layout step: frames (N, C, T, H, W) fp32 -> channels-last rows (N*T*H*W, ld), zeros in columns [C, ld) */
+int sf_op_video_to_cl(const float *x, int N, int C, int T, int H, int W, int ld, float *out, void *stream);
+/* AdaptiveAvgPool3d((None, 1, 1)): x rows (NT*HW, ld) -> out (NT, C);  _bwd: dx rows (NT*HW, ld) = dout[nt] / HW (zeros in [C, ld)) */
+int sf_op_video_pool(const float *x, int64_t NT, int HW, int C, int ld, float *out, void *stream);
+int sf_op_video_pool_bwd(const float *dout, int64_t NT, int HW, int C, int ld, float *dx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,11 @@ class EncoderConfig(C.Structure):
     ]
 
 
+class VConvDesc(C.Structure):
+    """sf_vconv_desc: one video-geometry convolution of the onset net's training path."""
+    _fields_ = [(n, C.c_int32) for n in ("N", "T", "Hi", "Wi", "cin", "cin_ld", "cout", "cout_ld", "kt", "kh", "kw", "sh", "sw", "pt", "ph", "pw")]
+
+
 # every symbol include/syncfusion_amd.h declares: (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -128,6 +133,18 @@ SYMBOLS = {
     "sf_bench_conv_cb": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float)]),
     "sf_op_ln_modulate": (_I, [_I, _P, _P, _F, _I, _I, _I, _P, _P]),
     "sf_op_attention": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    # VideoOnsetNet training (fp32, channels-last video rows)
+    "sf_op_vconv_workspace_bytes": (_L, [C.POINTER(VConvDesc)]),
+    "sf_op_vconv_fwd": (_I, [C.POINTER(VConvDesc), _P, _P, _P, _P, _L, _P]),
+    "sf_op_vconv_bwd": (_I, [C.POINTER(VConvDesc), _P, _P, _P, _P, _P, _P, _L, _P]),
+    "sf_op_bn_train_workspace_bytes": (_L, [_L, _I]),
+    # (x, res, rows, C, ld, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, relu, y, save_mean, save_invstd, ws, ws_bytes, stream)
+    "sf_op_bn_train_fwd": (_I, [_P, _P, _L, _I, _I, _P, _P, _F, _F, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
+    # (x, y, dy, rows, C, ld, gamma, save_mean, save_invstd, dx, dres, dgamma, dbeta, ws, ws_bytes, stream)
+    "sf_op_bn_train_bwd": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "sf_op_video_to_cl": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "sf_op_video_pool": (_I, [_P, _L, _I, _I, _I, _P, _P]),
+    "sf_op_video_pool_bwd": (_I, [_P, _L, _I, _I, _I, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -440,6 +440,41 @@ bool attention_f32_mfma_ok(int ldq, int ldkv, int ldo, int B, int H);
 hipError_t launch_attention_f32_mfma(const float *q, int ldq, const float *kv, int ldkv, int B, int L, int H, float *out, int ldo, hipStream_t s,
                                      float *lse_out, bool x3 = false, bool xfmt = false);
 
+// ---------------------------------------------------------------------------------------
+// VideoOnsetNet training (onset_train.hip): fp32, channels-last video rows ((n*T + t)*H + h)*W + w, channel counts padded to ld columns
+// (zeros in the padding).  Temporal stride 1.
+// ---------------------------------------------------------------------------------------
+struct VConvGeom {
+  int cin = 0, cout = 0, T = 1, Hi = 1, Wi = 1, Ho = 1, Wo = 1, kt = 1, kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, ph = 0, pw = 0;
+  __host__ __device__ int taps() const { return kt * kh * kw; }
+};
+// GEMM row length of `taps` taps of `ld` channels (a multiple of 32, zero padded)
+int vconv_k(int taps, int ld);
+// PyTorch weight (cout, cin, kt, kh, kw) -> the forward GEMM's [cout][vconv_k(taps, cin_ld)] ([taps][cin_ld] first)
+hipError_t launch_vconv_pack_fwd(const float *w, const VConvGeom &g, int cin_ld, float *out, hipStream_t s);
+// y (NT*Ho*Wo, cout_ld) = conv(x (NT*Hi*Wi, cin_ld); packed weights), no bias (launch_conv_gemm, geom 1)
+hipError_t launch_vconv_fwd(const float *x, int cin_ld, const float *wpk, const VConvGeom &g, int64_t NT, float *y, int cout_ld, hipStream_t s);
+// data gradient of a stride-1 convolution (2 p == k - 1 per axis): the forward GEMM on flipped taps; wflip: cin * vconv_k(taps, cout_ld) floats
+hipError_t launch_vconv_dgrad_s1(const float *dy, int cout_ld, const float *w, const VConvGeom &g, int64_t NT, float *wflip, float *dx, int cin_ld,
+                                 hipStream_t s);
+// data gradient in gather form (any spatial stride, kt == 1, cout_ld % 8 == 0); wg: taps * cout_ld * cin_ld floats
+hipError_t launch_vconv_dgrad_gather(const float *dy, int cout_ld, const float *w, const VConvGeom &g, int64_t NT, float *wg, float *dx, int cin_ld,
+                                     hipStream_t s);
+// weight gradient dw (cout, cin, kt, kh, kw) = sum_rows dy[row][co] x[src(row, tap)][ci]; partial: S * cout * taps * cin_ld floats
+int vwgrad_splits(int64_t rows, const VConvGeom &g, int cin_ld);
+hipError_t launch_vconv_wgrad(const float *dy, int cout_ld, const float *x, int cin_ld, const VConvGeom &g, int64_t NT, float *partial, int S, float *dw,
+                              hipStream_t s);
+// BatchNorm3d train forward: statistics over all rows, running statistics (momentum, unbiased variance), nbt += 1, y = act(xhat gamma + beta + res);
+// ws: 2 * S * C + 2 * C floats (S = bn_train_slices); backward: ws 2 * S * C + 3 * C floats
+int bn_train_slices(int64_t rows, int C);
+hipError_t launch_bn_train_fwd(const float *x, const float *res, int ld, int C, int64_t rows, const float *gamma, const float *beta, float eps,
+                               float momentum, float *run_mean, float *run_var, int64_t *nbt, int relu, float *y, float *save_mean, float *save_invstd,
+                               float *ws, hipStream_t s);
+hipError_t launch_bn_train_bwd(const float *x, const float *y /* ReLU mask or null */, const float *dy, int ld, int C, int64_t rows, const float *gamma,
+                               const float *mean, const float *invstd, float *dx, float *dres, float *dgamma, float *dbeta, float *ws, hipStream_t s);
+// backward of launch_spatial_mean: dx[(nt * HW + p) * ld + c] = dp[nt][c] / HW (zero for c >= C)
+hipError_t launch_pool_bwd(const float *dp, int64_t NT, int HW, int C, int ld, float *dx, hipStream_t s);
+
 // BatchNorm (eval) -> per-channel scale / shift
 hipError_t launch_bn_fold(const float *gamma, const float *beta, const float *mean, const float *var, float eps, int C,
                           float *scale, float *shift, hipStream_t s);

@@ -1,0 +1,126 @@
+"""Boundary object of the onset net's training: mirror of ``main.module_onset.Model`` (main/module_onset.py:22-130, 268-354).
+
+Same constructor arguments and attribute (``model``: checkpoint keys ``model.net.model.*`` / ``model.fc.*``), the same AdamW set-up, the
+same ``common_step`` / ``training_step`` / ``validation_step`` / ``test_step`` returning the loss, and the same ``BCLoss`` (class-balanced
+``BCEWithLogitsLoss``) with its ``evaluate`` metrics (AP, Acc, OnsNumAcc).  ``pytorch_lightning`` is the base class when it imports,
+otherwise the ``torch.nn.Module`` fallback of ``syncfusion_amd/module.py`` (``log`` is a no-op).  The wandb / CSV writers of the reference
+(``log_labels``, ``log_annotations``, ``concat_annotations``) are not mirrored; ``syncfusion_amd.onsets_to_track`` covers the logits -> onset
+times glue.
+"""
+from __future__ import annotations
+
+from typing import Dict
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .module import _Base
+from .onset_net import VideoOnsetNet
+
+Tensor = torch.Tensor
+
+
+def average_precision(target: np.ndarray, score: np.ndarray) -> float:
+    """``sklearn.metrics.average_precision_score`` for binary labels: sum over the distinct score thresholds (descending) of
+    (recall step) * precision, ties resolved as one threshold."""
+    target = np.asarray(target).reshape(-1).astype(np.float64)
+    score = np.asarray(score).reshape(-1).astype(np.float64)
+    order = np.argsort(-score, kind="mergesort")
+    score, target = score[order], target[order]
+    last = np.r_[np.nonzero(np.diff(score))[0], score.size - 1]   # last index of every distinct score
+    tps = np.cumsum(target)[last]
+    fps = (last + 1) - tps
+    if tps.size == 0 or tps[-1] == 0:
+        return float("nan")   # (sklearn warns and returns nan-equivalent: no positive sample)
+    precision = tps / (tps + fps)
+    recall = tps / tps[-1]
+    recall_prev = np.r_[0.0, recall[:-1]]
+    return float(np.sum((recall - recall_prev) * precision))
+
+
+class BCLoss(nn.Module):
+    """main/module_onset.py:268-354.  ``forward``: ``BCEWithLogitsLoss(pos_weight = (n - sum t) / sum t)`` over the flattened logits; as in
+    the reference, a batch without positive labels gives ``pos_weight = inf`` and the loss is inf / nan."""
+
+    def __init__(self):
+        super().__init__()
+        self.threshold = 0.75
+
+    def forward(self, pred: Tensor, target: Tensor) -> Tensor:
+        pred = pred.contiguous().view(-1)
+        target = target.contiguous().view(-1)
+        pos_weight = (target.shape[0] - target.sum()) / target.sum()
+        criterion = nn.BCEWithLogitsLoss(pos_weight=pos_weight).to(pred.device)
+        return criterion(pred, target.float())
+
+    def evaluate(self, pred: Tensor, target: Tensor) -> Dict[str, float]:
+        ons_num_acc = self.onset_num_acc(pred, target)
+        pred = torch.sigmoid(pred.detach().contiguous().view(-1)).cpu().numpy()
+        target = target.detach().contiguous().view(-1).cpu().numpy()
+        pos_index = np.nonzero(target == 1)[0]
+        neg_index = np.nonzero(target == 0)[0]
+        balance_num = min(pos_index.shape[0], neg_index.shape[0])   # the first balance_num positives and negatives
+        index = np.concatenate((pos_index[:balance_num], neg_index[:balance_num]), axis=0)
+        pred, target = pred[index], target[index]
+        return {"AP": average_precision(target, pred), "Acc": self.binary_acc(pred, target), "OnsNumAcc": ons_num_acc}
+
+    def binary_acc(self, pred: np.ndarray, target: np.ndarray) -> float:
+        pred = np.where(pred > self.threshold, 1.0, 0.0)
+        return np.sum(pred == target) / target.shape[0]
+
+    def onset_num_acc(self, pred: Tensor, target: Tensor) -> float:
+        p = torch.sigmoid(pred.detach()).cpu().numpy()
+        t = target.detach().cpu().numpy().astype(int)
+        p = (p > self.threshold).astype(int)
+        for i in range(p.shape[0]):              # remove consecutive onsets (the later frame of a pair, left to right)
+            for j in range(p.shape[-1] - 1):
+                if p[i][j] == 1 and p[i][j + 1] == 1:
+                    p[i][j + 1] = 0
+        return np.sum(np.sum(p, axis=-1) == np.sum(t, axis=-1)) / len(p)
+
+
+class Model(_Base):
+    """Drop-in for ``main.module_onset.Model`` (cfg/model/model-onset.yaml ``class_path``)."""
+
+    def __init__(self, lr: float, lr_beta1: float, lr_beta2: float, lr_eps: float, lr_weight_decay: float, onset_model: VideoOnsetNet):
+        super().__init__()
+        self.lr = lr
+        self.lr_beta1 = lr_beta1
+        self.lr_beta2 = lr_beta2
+        self.lr_eps = lr_eps
+        self.lr_weight_decay = lr_weight_decay
+        self.model: VideoOnsetNet = onset_model
+        self.loss = BCLoss()
+
+    def configure_optimizers(self) -> torch.optim.Optimizer:
+        params = list(self.model.parameters())
+        fused = bool(params) and all(p.is_cuda for p in params)   # the single-kernel multi-tensor AdamW on the GPU (module.py)
+        return torch.optim.AdamW(params, lr=self.lr, betas=(self.lr_beta1, self.lr_beta2), eps=self.lr_eps, weight_decay=self.lr_weight_decay,
+                                 **({"fused": True} if fused else {}))
+
+    def common_step(self, batch, batch_idx, mode: str = "train"):
+        frames, labels = batch["frames"], batch["label"]
+        pred = self.model(frames)
+        loss = self.loss(pred, labels)
+        metrics = self.loss.evaluate(pred, labels)
+        return loss, metrics
+
+    def log_metrics(self, metrics: Dict[str, float], mode: str = "val") -> None:
+        for key, value in metrics.items():
+            self.log(f"metrics/{mode}/{key}", value, on_step=False, on_epoch=True, prog_bar=True, logger=True, sync_dist=True)
+
+    def _step(self, batch, batch_idx, mode: str) -> Tensor:
+        loss, metrics = self.common_step(batch, batch_idx, mode=mode)
+        self.log(f"loss/{mode}", loss, on_step=False, on_epoch=True, prog_bar=True, logger=True, sync_dist=True)
+        self.log_metrics(metrics, mode=mode)
+        return loss
+
+    def training_step(self, batch, batch_idx) -> Tensor:
+        return self._step(batch, batch_idx, "train")
+
+    def validation_step(self, batch, batch_idx) -> Tensor:
+        return self._step(batch, batch_idx, "val")
+
+    def test_step(self, batch, batch_idx) -> Tensor:
+        return self._step(batch, batch_idx, "test")

@@ -6,8 +6,10 @@ and exposes the *same* ``state_dict`` keys as the reference (226 tensors,
 ``net.model.stem.0.weight`` ... ``fc.2.bias``; main/resnet.py:195-286,
 main/onset_net.py:12-38), so ``load_state_dict`` of a reference checkpoint works.
 
-The ``torch.nn`` modules below only HOLD parameters.  ``forward`` never runs them:
-it hands raw device pointers to the HIP engine behind the C ABI
+The ``torch.nn`` modules below only HOLD parameters.  ``forward`` never runs them.
+In train mode (under grad mode) it runs the differentiable composition of
+``syncfusion_amd/onset_training.py`` (HIP convolutions, BatchNorm and their backward).
+In eval mode it hands raw device pointers to the HIP engine behind the C ABI
 (``sf_onsetnet_forward`` in include/syncfusion_amd.h), which folds the eval-mode
 BatchNorms into the convolutions and runs every (1,k,k)/(3,1,1)/1x1x1 convolution
 as an MFMA implicit GEMM on channels-last activations.  There is no CPU path: a
@@ -23,6 +25,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._engine import OnsetNetEngine
+from .onset_training import onset_train_forward
 
 # (name, planes, spatial stride of the first block) -- main/resnet.py:215-222
 _STAGES = (("layer1", 64, 1), ("layer2", 128, 2), ("layer3", 256, 2), ("layer4", 512, 2))
@@ -78,7 +81,8 @@ class _KeepTemp(nn.Module):
 
 
 class VideoOnsetNet(nn.Module):
-    """Drop-in for ``main.onset_net.VideoOnsetNet`` (HIP forward, inference only)."""
+    """Drop-in for ``main.onset_net.VideoOnsetNet``.  ``.eval()``: the HIP inference engine (BatchNorm folded, no graph).  ``.train()``
+    under grad mode: the differentiable HIP composition of syncfusion_amd/onset_training.py (batch statistics, running-statistics update)."""
 
     def __init__(self, pretrained: bool = False, dtype: str = "fp32"):
         super().__init__()
@@ -101,11 +105,16 @@ class VideoOnsetNet(nn.Module):
             self._engine = OnsetNetEngine(self, self.compute_dtype)
         return self._engine
 
-    @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() != 5 or x.shape[1] != 3:
             raise ValueError(f"VideoOnsetNet expects (N, 3, T, H, W), got {tuple(x.shape)}")
         _lib.require_gpu_tensor(x, "VideoOnsetNet.forward")
         if self.training:
-            raise RuntimeError("VideoOnsetNet (HIP) implements the eval-mode forward only (BatchNorm running stats); call .eval()")
-        return self._get_engine().forward(x)
+            if not torch.is_grad_enabled():
+                raise RuntimeError("VideoOnsetNet (HIP): train mode runs the training composition and needs grad mode "
+                                   "(batch statistics, running-statistics update, autograd graph); call .eval() for inference")
+            if self.compute_dtype != "fp32":
+                raise RuntimeError(f"VideoOnsetNet (HIP): training runs in fp32 only (compute_dtype={self.compute_dtype!r})")
+            return onset_train_forward(self, x)
+        with torch.no_grad():
+            return self._get_engine().forward(x)

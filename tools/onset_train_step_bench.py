@@ -1,0 +1,94 @@
+"""Milliseconds per VideoOnsetNet training step at the reference's configuration: batch 16 x (3, 30, 112, 112) (cfg/data/
+data-onset-greatesthit.yaml: 2 s chunks at 15 fps), forward + BCLoss + backward + fused AdamW -- the HIP path (VideoOnsetNet.train(),
+syncfusion_amd/onset_training.py) and, in the same run, the same step on torch's own nn.Conv3d / nn.BatchNorm3d modules (MIOpen).
+
+Device events around `--steps` steps after `--warmup` steps; FLOPs per step = 3 x the forward's convolutions (forward, data and weight
+gradients; the stem has no data gradient, so this slightly overstates the work); peak memory from torch.cuda.max_memory_allocated.
+
+    python tools/onset_train_step_bench.py [--batch 16] [--steps 5] [--warmup 2] [--skip-torch]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from oracle.onsetnet_ref import onsetnet_flops  # noqa: E402
+from syncfusion_amd import OnsetModel, VideoOnsetNet  # noqa: E402
+
+
+def torch_modules_forward(net, x):
+    """main/onset_net.py:57-63 on the nn modules that hold the parameters (train-mode BatchNorm, MIOpen convolutions)."""
+    m = net.net.model
+    h = m.stem(x)
+    for name in ("layer1", "layer2", "layer3", "layer4"):
+        for blk in getattr(m, name):
+            res = h if blk.downsample is None else blk.downsample(h)
+            h = F.relu(blk.conv2(blk.conv1(h)) + res)
+    return net.fc(h.mean(dim=(3, 4)).transpose(-1, -2)).squeeze(-1)
+
+
+def time_steps(model, forward, batch, steps, warmup):
+    opt = model.configure_optimizers()
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = model.loss(forward(batch["frames"]), batch["label"])
+        loss.backward()
+        opt.step()
+
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(steps):
+        step()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / steps, torch.cuda.max_memory_allocated() / 2**30
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--frames", type=int, default=30)
+    ap.add_argument("--size", type=int, default=112)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--skip-torch", action="store_true")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    N, T, S = a.batch, a.frames, a.size
+    batch = {"frames": torch.randn(N, 3, T, S, S, device=dev), "label": (torch.rand(N, T, device=dev) < 0.2).float()}
+    batch["label"][0, 0] = 1.0
+    fwd_flop = N * (onsetnet_flops(T, S, S) - 2.0 * T * (512 * 128 + 128))   # the convolutions
+    step_flop = 3 * fwd_flop
+    out = {"shape": [N, 3, T, S, S], "tflop_per_step": step_flop / 1e12}
+    net = VideoOnsetNet(False).to(dev).train()
+    model = OnsetModel(1e-4, 0.9, 0.999, 1e-8, 1e-2, net).to(dev)
+    ms, gib = time_steps(model, net, batch, a.steps, a.warmup)
+    out["hip"] = {"ms_per_step": round(ms, 2), "tflops": round(step_flop / ms / 1e9, 2), "peak_gib": round(gib, 2)}
+    print(f"HIP path    : {ms:8.2f} ms/step  {step_flop / ms / 1e9:6.2f} TFLOP/s  peak {gib:6.2f} GiB", flush=True)
+    if not a.skip_torch:
+        del model, net
+        torch.cuda.empty_cache()
+        net = VideoOnsetNet(False).to(dev).train()
+        model = OnsetModel(1e-4, 0.9, 0.999, 1e-8, 1e-2, net).to(dev)
+        ms_t, gib_t = time_steps(model, lambda x: torch_modules_forward(net, x), batch, a.steps, a.warmup)
+        out["torch_modules"] = {"ms_per_step": round(ms_t, 2), "tflops": round(step_flop / ms_t / 1e9, 2), "peak_gib": round(gib_t, 2)}
+        print(f"torch (MIOpen): {ms_t:8.2f} ms/step  {step_flop / ms_t / 1e9:6.2f} TFLOP/s  peak {gib_t:6.2f} GiB", flush=True)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
