@@ -401,6 +401,28 @@ int sf_op_bn_train_fwd(const float *x, const float *res, int64_t rows, int C, in
                        void *ws, int64_t ws_bytes, void *stream);
 int sf_op_bn_train_bwd(const float *x, const float *y, const float *dy, int64_t rows, int C, int ld, const float *gamma, const float *save_mean,
                        const float *save_invstd, float *dx, float *dres, float *dgamma, float *dbeta, void *ws, int64_t ws_bytes, void *stream);
+/* The same BatchNorm with statistics shared by the `world` ranks of a data-parallel group (torch.nn.SyncBatchNorm), in split phases: each direction
+ * is cut where the per-channel numbers are small, and the CALLER runs one all-gather of 2 * C floats there (this library links no collective library).
+ *   sf_op_bn_sync_stats      local_stats (C, 2) = (mean, M2 = sum (x - mean)^2) of this rank's rows; rows >= 1 (a rank may hold a single row)
+ *   sf_op_bn_sync_fwd_apply  gathered_stats (world, C, 2): every rank's local_stats in rank order;  row_counts (world) int64, DEVICE memory: every
+ *                            rank's row count (exact integers; their sum must be >= 2).  Merges the table in rank order (the mean about rank 0's mean,
+ *                            then M2 = sum M2_r + n_r (mean_r - mean)^2), then as sf_op_bn_train_fwd: save_mean / save_invstd, the running statistics
+ *                            (unbiased over the TOTAL row count), *num_batches_tracked += 1, y.  Identical input gives identical bits on every rank.
+ *   sf_op_bn_sync_bwd_sums   local_sums (C, 2) = (sum dz, sum dz * xhat) of this rank's rows;  dgamma / dbeta (C, or NULL) are these LOCAL sums, as
+ *                            in torch.nn.SyncBatchNorm (the gradient all-reduce averages them afterwards)
+ *   sf_op_bn_sync_bwd_apply  gathered_sums (world, C, 2) added in rank order, divided by the total row count, then dx / dres as sf_op_bn_train_bwd
+ * No atomics; the merge order is fixed, so the results are bit-reproducible.  ws >= sf_op_bn_sync_workspace_bytes(rows, C) for all four calls. */
+int64_t sf_op_bn_sync_workspace_bytes(int64_t rows, int C);
+int sf_op_bn_sync_stats(const float *x, int64_t rows, int C, int ld, float *local_stats, void *ws, int64_t ws_bytes, void *stream);
+int sf_op_bn_sync_fwd_apply(const float *x, const float *res, int64_t rows, int C, int ld, const float *gathered_stats, const int64_t *row_counts, int world,
+                            const float *gamma, const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                            int64_t *num_batches_tracked, int relu, float *y, float *save_mean, float *save_invstd, void *ws, int64_t ws_bytes,
+                            void *stream);
+int sf_op_bn_sync_bwd_sums(const float *x, const float *y, const float *dy, int64_t rows, int C, int ld, const float *save_mean, const float *save_invstd,
+                           float *local_sums, float *dgamma, float *dbeta, void *ws, int64_t ws_bytes, void *stream);
+int sf_op_bn_sync_bwd_apply(const float *x, const float *y, const float *dy, int64_t rows, int C, int ld, const float *gathered_sums,
+                            const int64_t *row_counts, int world, const float *gamma, const float *save_mean, const float *save_invstd, float *dx,
+                            float *dres, void *ws, int64_t ws_bytes, void *stream);
 /* layout step: frames (N, C, T, H, W) fp32 -> channels-last rows (N*T*H*W, ld), zeros in columns [C, ld) */
 int sf_op_video_to_cl(const float *x, int N, int C, int T, int H, int W, int ld, float *out, void *stream);
 /* AdaptiveAvgPool3d((None, 1, 1)): x rows (NT*HW, ld) -> out (NT, C);  _bwd: dx rows (NT*HW, ld) = dout[nt] / HW (zeros in [C, ld)) */

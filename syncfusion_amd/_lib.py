@@ -142,6 +142,17 @@ SYMBOLS = {
     "sf_op_bn_train_fwd": (_I, [_P, _P, _L, _I, _I, _P, _P, _F, _F, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
     # (x, y, dy, rows, C, ld, gamma, save_mean, save_invstd, dx, dres, dgamma, dbeta, ws, ws_bytes, stream)
     "sf_op_bn_train_bwd": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    # the same BatchNorm with cross-rank statistics, in split phases around the caller's all-gather
+    "sf_op_bn_sync_workspace_bytes": (_L, [_L, _I]),
+    # (x, rows, C, ld, local_stats, ws, ws_bytes, stream)
+    "sf_op_bn_sync_stats": (_I, [_P, _L, _I, _I, _P, _P, _L, _P]),
+    # (x, res, rows, C, ld, gathered_stats, row_counts, world, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, relu, y,
+    #  save_mean, save_invstd, ws, ws_bytes, stream)
+    "sf_op_bn_sync_fwd_apply": (_I, [_P, _P, _L, _I, _I, _P, _P, _I, _P, _P, _F, _F, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
+    # (x, y, dy, rows, C, ld, save_mean, save_invstd, local_sums, dgamma, dbeta, ws, ws_bytes, stream)
+    "sf_op_bn_sync_bwd_sums": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
+    # (x, y, dy, rows, C, ld, gathered_sums, row_counts, world, gamma, save_mean, save_invstd, dx, dres, ws, ws_bytes, stream)
+    "sf_op_bn_sync_bwd_apply": (_I, [_P, _P, _P, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
     "sf_op_video_to_cl": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sf_op_video_pool": (_I, [_P, _L, _I, _I, _I, _P, _P]),
     "sf_op_video_pool_bwd": (_I, [_P, _L, _I, _I, _I, _P, _P]),

@@ -146,6 +146,69 @@ int sf_op_bn_train_bwd(const float *x, const float *y, const float *dy, int64_t 
   SF_API_END
 }
 
+int64_t sf_op_bn_sync_workspace_bytes(int64_t rows, int C) {
+  if (rows < 1 || C < 1) return -1;
+  return ((int64_t)2 * bn_train_slices(rows, C) * C + 3 * (int64_t)C) * (int64_t)sizeof(float);
+}
+
+namespace {
+// the argument checks shared by the four split-phase entry points (a rank may hold a single row; the caller keeps the TOTAL at 2 or more)
+void check_bn_sync(int64_t rows, int C, int ld, const void *ws, int64_t ws_bytes) {
+  if (rows < 1 || C < 1 || ld < C || ld % 4) fail(SF_ERR_INVALID, "rows >= 1, C >= 1, ld >= C and ld %% 4 == 0 required");
+  if (!ws) fail(SF_ERR_INVALID, "null argument");
+  const int64_t need = sf_op_bn_sync_workspace_bytes(rows, C);
+  if (ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+}
+}  // namespace
+
+int sf_op_bn_sync_stats(const float *x, int64_t rows, int C, int ld, float *local_stats, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!x || !local_stats) fail(SF_ERR_INVALID, "null argument");
+  check_bn_sync(rows, C, ld, ws, ws_bytes);
+  SF_HIP(launch_bn_sync_stats(x, ld, C, rows, local_stats, static_cast<float *>(ws), static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_bn_sync_fwd_apply(const float *x, const float *res, int64_t rows, int C, int ld, const float *gathered_stats, const int64_t *row_counts, int world,
+                            const float *gamma, const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                            int64_t *num_batches_tracked, int relu, float *y, float *save_mean, float *save_invstd, void *ws, int64_t ws_bytes,
+                            void *stream) {
+  SF_API_BEGIN
+  if (!x || !gathered_stats || !row_counts || !gamma || !beta || !y || !save_mean || !save_invstd) fail(SF_ERR_INVALID, "null argument");
+  if (world < 1) fail(SF_ERR_INVALID, "world >= 1 required");
+  check_bn_sync(rows, C, ld, ws, ws_bytes);
+  SF_HIP(launch_bn_sync_fwd_apply(x, res, ld, C, rows, gathered_stats, row_counts, world, gamma, beta, eps, momentum, running_mean, running_var,
+                                  num_batches_tracked, relu, y, save_mean, save_invstd, static_cast<float *>(ws), static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_bn_sync_bwd_sums(const float *x, const float *y, const float *dy, int64_t rows, int C, int ld, const float *save_mean, const float *save_invstd,
+                           float *local_sums, float *dgamma, float *dbeta, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!x || !dy || !save_mean || !save_invstd || !local_sums) fail(SF_ERR_INVALID, "null argument");
+  check_bn_sync(rows, C, ld, ws, ws_bytes);
+  SF_HIP(launch_bn_sync_bwd_sums(x, y, dy, ld, C, rows, save_mean, save_invstd, local_sums, dgamma, dbeta, static_cast<float *>(ws),
+                                 static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_bn_sync_bwd_apply(const float *x, const float *y, const float *dy, int64_t rows, int C, int ld, const float *gathered_sums,
+                            const int64_t *row_counts, int world, const float *gamma, const float *save_mean, const float *save_invstd, float *dx,
+                            float *dres, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!x || !dy || !gathered_sums || !row_counts || !gamma || !save_mean || !save_invstd) fail(SF_ERR_INVALID, "null argument");
+  if (world < 1) fail(SF_ERR_INVALID, "world >= 1 required");
+  if (!dx && !dres) fail(SF_ERR_INVALID, "nothing to compute: dx and dres are both null");
+  check_bn_sync(rows, C, ld, ws, ws_bytes);
+  SF_HIP(launch_bn_sync_bwd_apply(x, y, dy, ld, C, rows, gathered_sums, row_counts, world, gamma, save_mean, save_invstd, dx, dres,
+                                  static_cast<float *>(ws), static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
 int sf_op_video_to_cl(const float *x, int N, int C, int T, int H, int W, int ld, float *out, void *stream) {
   SF_API_BEGIN
   if (!x || !out) fail(SF_ERR_INVALID, "null argument");

@@ -472,6 +472,20 @@ hipError_t launch_bn_train_fwd(const float *x, const float *res, int ld, int C, 
                                float *ws, hipStream_t s);
 hipError_t launch_bn_train_bwd(const float *x, const float *y /* ReLU mask or null */, const float *dy, int ld, int C, int64_t rows, const float *gamma,
                                const float *mean, const float *invstd, float *dx, float *dres, float *dgamma, float *dbeta, float *ws, hipStream_t s);
+// The same BatchNorm with statistics shared by the `world` ranks of a data-parallel group, in split phases around the caller's all-gather:
+//   stats      local[c] = (mean, M2) of this rank's rows (rows >= 1)                                    ws: 2 * S * C floats
+//   fwd_apply  gathered (world, C, 2) + counts (world int64 row counts, device) -> merged in rank order; the rest as launch_bn_train_fwd   ws: C floats
+//   bwd_sums   local[c] = (sum dz, sum dz xhat) of this rank's rows; dgamma / dbeta = these local sums  ws: 2 * S * C floats
+//   bwd_apply  gathered (world, C, 2) sums added in rank order / total rows -> dx, dres                 ws: 3 * C floats
+hipError_t launch_bn_sync_stats(const float *x, int ld, int C, int64_t rows, float *local, float *ws, hipStream_t s);
+hipError_t launch_bn_sync_fwd_apply(const float *x, const float *res, int ld, int C, int64_t rows, const float *gathered, const int64_t *counts, int world,
+                                    const float *gamma, const float *beta, float eps, float momentum, float *run_mean, float *run_var, int64_t *nbt,
+                                    int relu, float *y, float *save_mean, float *save_invstd, float *ws, hipStream_t s);
+hipError_t launch_bn_sync_bwd_sums(const float *x, const float *y /* ReLU mask or null */, const float *dy, int ld, int C, int64_t rows, const float *mean,
+                                   const float *invstd, float *local, float *dgamma, float *dbeta, float *ws, hipStream_t s);
+hipError_t launch_bn_sync_bwd_apply(const float *x, const float *y /* ReLU mask or null */, const float *dy, int ld, int C, int64_t rows,
+                                    const float *gathered, const int64_t *counts, int world, const float *gamma, const float *mean, const float *invstd,
+                                    float *dx, float *dres, float *ws, hipStream_t s);
 // backward of launch_spatial_mean: dx[(nt * HW + p) * ld + c] = dp[nt][c] / HW (zero for c >= C)
 hipError_t launch_pool_bwd(const float *dp, int64_t NT, int HW, int C, int ld, float *dx, hipStream_t s);
 

@@ -9,6 +9,8 @@
 //             -> vdgrad_gather_kernel: input pixels grouped by (h % s, w % s) so that every 32-row tile has one tap set; no zero-dilated dY
 //   BatchNorm3d (train): per-channel slice statistics (mean, M2) with a shift inside each slice, merged about the first slice's mean in order;
 //             apply (+ residual, ReLU); backward sums  sum dz, sum dz xhat  per slice, merged in order, then dx (+ the residual's dz) in one pass
+//   BatchNorm3d (train) across the ranks of a data-parallel group: the same slice kernels, a per-rank merge, and a rank-order merge of the gathered
+//             (world, C, 2) table on either side of the caller's all-gather (statistics forward, sum dz / sum dz xhat backward)
 //   spatial mean pool backward: a broadcast of dP / (H W)
 // No atomics: two identical passes give bit-identical results.
 #include "common.h"
@@ -379,6 +381,100 @@ __global__ void bn_bwd_apply_kernel(const float *__restrict__ x, const float *__
   }
 }
 
+// ---- BatchNorm3d, train mode, statistics shared by the ranks of a data-parallel group ---------------------------------------------------------
+// Each direction is cut where the per-channel numbers are small: a rank reduces its own rows to one pair per channel, the caller gathers the
+// (world, C, 2) table of all ranks, and every rank merges that table in rank order: identical input, identical order, identical bits on every rank.
+// The row counts travel beside the table as exact int64 values.
+
+// local statistics: out[c] = (mean, M2) of this rank's rows; the slices in order, in bn_stats_final_kernel's two-pass form
+__global__ void bn_stats_merge_kernel(const float2 *__restrict__ part, int S, int64_t rows, int64_t rps, int C, float2 *__restrict__ out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float m0 = part[c].x;
+  float dsum = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const int64_t r0 = (int64_t)s * rps;
+    if (r0 >= rows) break;
+    dsum += (float)(min(rows, r0 + rps) - r0) * (part[(int64_t)s * C + c].x - m0);
+  }
+  const float mean = m0 + dsum / (float)rows;
+  float m2 = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const int64_t r0 = (int64_t)s * rps;
+    if (r0 >= rows) break;
+    const float2 p = part[(int64_t)s * C + c];
+    const float d = p.x - mean;
+    m2 += p.y + (float)(min(rows, r0 + rps) - r0) * d * d;
+  }
+  out[c] = make_float2(mean, m2);
+}
+
+// merge the ranks' (mean, M2) in rank order (the mean about rank 0's mean, then M2 = sum M2_r + n_r (mean_r - mean)^2), save (mean, 1/std), update
+// the running statistics with the unbiased variance over the total row count, and leave gamma / std for the apply pass
+__global__ void bn_sync_final_kernel(const float2 *__restrict__ tab, const int64_t *__restrict__ counts, int world, int C, const float *__restrict__ gamma,
+                                     float eps, float momentum, float *__restrict__ run_mean, float *__restrict__ run_var, int64_t *__restrict__ nbt,
+                                     float *__restrict__ save_mean, float *__restrict__ save_invstd, float *__restrict__ scale) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c == 0 && nbt) *nbt += 1;
+  if (c >= C) return;
+  const float m0 = tab[c].x;
+  int64_t total = 0;
+  float dsum = 0.f;
+  for (int r = 0; r < world; ++r) {
+    const int64_t n = counts[r];
+    total += n;
+    dsum += (float)n * (tab[(int64_t)r * C + c].x - m0);
+  }
+  const float mean = m0 + dsum / (float)total;
+  float m2 = 0.f;
+  for (int r = 0; r < world; ++r) {
+    const float2 p = tab[(int64_t)r * C + c];
+    const float d = p.x - mean;
+    m2 += p.y + (float)counts[r] * d * d;
+  }
+  const float var = m2 / (float)total;
+  const float inv = 1.f / sqrtf(var + eps);
+  save_mean[c] = mean;
+  save_invstd[c] = inv;
+  if (run_mean) run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mean;
+  if (run_var) run_var[c] = (1.f - momentum) * run_var[c] + momentum * (m2 / (float)(total - 1));
+  scale[c] = gamma[c] * inv;
+}
+
+// local backward sums: out[c] = (sum dz, sum dz xhat) over this rank's rows (slices in order); dbeta / dgamma are these LOCAL sums, as in
+// torch.nn.SyncBatchNorm (the gradient all-reduce averages them afterwards)
+__global__ void bn_bwd_merge_kernel(const float *__restrict__ part, int S, int C, float2 *__restrict__ out, float *__restrict__ dgamma,
+                                    float *__restrict__ dbeta) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  float a = 0.f, b = 0.f;
+  for (int s = 0; s < S; ++s) {
+    a += part[((int64_t)s * 2) * C + c];
+    b += part[((int64_t)s * 2 + 1) * C + c];
+  }
+  out[c] = make_float2(a, b);
+  if (dbeta) dbeta[c] = a;
+  if (dgamma) dgamma[c] = b;
+}
+
+// the ranks' sums added in rank order, over the total row count: coef = (gamma invstd, mean(dz), mean(dz xhat)) for bn_bwd_apply_kernel
+__global__ void bn_sync_bwd_coef_kernel(const float2 *__restrict__ tab, const int64_t *__restrict__ counts, int world, int C,
+                                        const float *__restrict__ gamma, const float *__restrict__ invstd, float *__restrict__ coef) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  int64_t total = 0;
+  float a = 0.f, b = 0.f;
+  for (int r = 0; r < world; ++r) {
+    const float2 p = tab[(int64_t)r * C + c];
+    total += counts[r];
+    a += p.x;
+    b += p.y;
+  }
+  coef[c] = gamma[c] * invstd[c];
+  coef[C + c] = a / (float)total;
+  coef[2 * C + c] = b / (float)total;
+}
+
 // spatial mean pool backward: dx[(nt * HW + p) * ld + c] = c < C ? dp[nt * C + c] / HW : 0
 __global__ void pool_bwd_kernel(const float *__restrict__ dp, int64_t NT, int HW, int C, int ld, float *__restrict__ dx) {
   const int64_t total = NT * HW * ld;
@@ -532,6 +628,52 @@ hipError_t launch_bn_train_bwd(const float *x, const float *y, const float *dy, 
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, S, rows, C, gamma, invstd, dgamma, dbeta, coef);
   if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, grid1d(rows * (ld / 4)), dim3(kTPB), 0, s, x, y, dy, ld, C, rows, mean, invstd, coef, dx, dres);
+  return hipGetLastError();
+}
+
+hipError_t launch_bn_sync_stats(const float *x, int ld, int C, int64_t rows, float *local, float *ws, hipStream_t s) {
+  const int S = bn_train_slices(rows, C);
+  const int64_t rps = (rows + S - 1) / S;
+  float2 *part = reinterpret_cast<float2 *>(ws);
+  hipLaunchKernelGGL(bn_stats_part_kernel, dim3((C + 63) / 64, S), dim3(256), 0, s, x, ld, C, rows, rps, part);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(bn_stats_merge_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, S, rows, rps, C, reinterpret_cast<float2 *>(local));
+  return hipGetLastError();
+}
+
+hipError_t launch_bn_sync_fwd_apply(const float *x, const float *res, int ld, int C, int64_t rows, const float *gathered, const int64_t *counts, int world,
+                                    const float *gamma, const float *beta, float eps, float momentum, float *run_mean, float *run_var, int64_t *nbt,
+                                    int relu, float *y, float *save_mean, float *save_invstd, float *ws, hipStream_t s) {
+  float *ss = ws;   // gamma / std: C floats
+  hipLaunchKernelGGL(bn_sync_final_kernel, dim3((C + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float2 *>(gathered), counts, world, C, gamma, eps,
+                     momentum, run_mean, run_var, nbt, save_mean, save_invstd, ss);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(bn_apply_kernel, grid1d(rows * (ld / 4)), dim3(kTPB), 0, s, x, res, ld, C, rows, save_mean, ss, beta, relu, y);
+  return hipGetLastError();
+}
+
+hipError_t launch_bn_sync_bwd_sums(const float *x, const float *y, const float *dy, int ld, int C, int64_t rows, const float *mean, const float *invstd,
+                                   float *local, float *dgamma, float *dbeta, float *ws, hipStream_t s) {
+  const int S = bn_train_slices(rows, C);
+  const int64_t rps = (rows + S - 1) / S;
+  hipLaunchKernelGGL(bn_bwd_part_kernel, dim3((C + 63) / 64, S), dim3(256), 0, s, x, y, dy, ld, C, rows, rps, mean, invstd, ws);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(bn_bwd_merge_kernel, dim3((C + 255) / 256), dim3(256), 0, s, ws, S, C, reinterpret_cast<float2 *>(local), dgamma, dbeta);
+  return hipGetLastError();
+}
+
+hipError_t launch_bn_sync_bwd_apply(const float *x, const float *y, const float *dy, int ld, int C, int64_t rows, const float *gathered,
+                                    const int64_t *counts, int world, const float *gamma, const float *mean, const float *invstd, float *dx, float *dres,
+                                    float *ws, hipStream_t s) {
+  float *coef = ws;   // 3 * C floats
+  hipLaunchKernelGGL(bn_sync_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float2 *>(gathered), counts, world, C, gamma,
+                     invstd, coef);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(bn_bwd_apply_kernel, grid1d(rows * (ld / 4)), dim3(kTPB), 0, s, x, y, dy, ld, C, rows, mean, invstd, coef, dx, dres);
   return hipGetLastError();
 }

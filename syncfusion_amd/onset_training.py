@@ -11,6 +11,10 @@ whose channel counts are padded to the inference engine's row lengths (``ld``; z
 * ``_VConv``    -- Conv3d without bias (``sf_op_vconv_fwd`` / ``sf_op_vconv_bwd``); saves its input and weight;
 * ``_BNTrain``  -- BatchNorm3d (+ residual) (+ ReLU) (``sf_op_bn_train_fwd`` / ``sf_op_bn_train_bwd``); saves its input, its output (the ReLU
   mask) and the batch mean / 1/std;
+* ``_BNSyncTrain`` -- the same BatchNorm with statistics shared by the ranks of a process group (``sf_op_bn_sync_*``): every direction is
+  cut where the per-channel numbers are small and one ``all_gather`` of ``2 C`` floats runs there (37 + 37 small collectives per step).  It is
+  selected per module: an ``nn.SyncBatchNorm`` (``torch.nn.SyncBatchNorm.convert_sync_batchnorm``) with an initialised process group of more
+  than one rank; everything else runs ``_BNTrain``, as ``torch.nn.SyncBatchNorm`` itself falls back to plain batch norm;
 * ``_Pool``     -- AdaptiveAvgPool3d((None, 1, 1)) (``sf_op_video_pool`` / ``sf_op_video_pool_bwd``).
 
 The fc head (0.01 % of the FLOPs), the pooled transpose and the loss run on ATen.  fp32 throughout (plain ``v_mfma_f32_32x32x2_f32``
@@ -19,9 +23,10 @@ products): the reference trains the onset net in fp32.  No atomics: a second bac
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
@@ -170,6 +175,168 @@ def batch_norm_train(x: Tensor, bn: nn.BatchNorm3d, res: Optional[Tensor] = None
     return _BNTrain.apply(x, bn.weight, bn.bias, res, bn, relu)
 
 
+# ---- cross-rank BatchNorm -----------------------------------------------------------------------------------------------------------------
+class SyncGroup:
+    """One process group's share of a synchronised forward: the clip counts of its ranks (gathered ONCE per forward, not once per layer) and
+    the collectives of the 37 BatchNorms.  ``group=None`` with no initialised process group is a world of one whose "gather" is a reshape
+    (the forced split-phase path of the tests and of tools/onset_train_step_bench.py)."""
+
+    def __init__(self, group, clips: int, device: torch.device):
+        self.group, self.device = group, device
+        self.live = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size(group) if self.live else 1
+        self.rank = dist.get_rank(group) if self.live else 0
+        # device tensors go straight into the collective on nccl (RCCL); gloo carries host tensors (as training.allreduce_gradients)
+        self.nccl = self.live and dist.get_backend(group) == "nccl"
+        self.stage_host = self.live and not self.nccl and device.type == "cuda"
+        self.collectives = 0
+        self.clips = self._gather_clips(int(clips))
+        empty = [r for r, n in enumerate(self.clips) if n < 1]
+        if empty:     # every rank sees the same table, so every rank raises: nobody is left waiting in a collective
+            raise ValueError(f"onset training (synchronised BatchNorm): rank(s) {empty} of {self.world} hold no clips (clip counts per rank "
+                             f"{self.clips}; this is rank {self.rank}): every rank needs at least one clip per step")
+        self._counts: Dict[int, Tensor] = {}
+
+    def _gather_clips(self, clips: int) -> List[int]:
+        if not self.live:
+            return [clips]
+        mine = torch.tensor([clips], dtype=torch.int64, device="cpu" if self.stage_host or self.device.type != "cuda" else self.device)
+        out = torch.empty(self.world, dtype=torch.int64, device=mine.device)
+        dist.all_gather(list(out.split(1)), mine, group=self.group)
+        self.collectives += 1
+        return [int(v) for v in out.cpu().tolist()]
+
+    def row_counts(self, rows_per_clip: int) -> Tensor:
+        """(world,) int64 on the device: every rank's row count of a layer = its clip count times the layer's T*H*W (exact integers)."""
+        t = self._counts.get(rows_per_clip)
+        if t is None:
+            t = torch.tensor([n * rows_per_clip for n in self.clips], dtype=torch.int64).to(self.device)
+            self._counts[rows_per_clip] = t
+        return t
+
+    def total_rows(self, rows_per_clip: int) -> int:
+        return sum(self.clips) * rows_per_clip
+
+    def all_gather(self, local: Tensor) -> Tensor:
+        """(C, 2) of this rank -> (world, C, 2) in rank order, on ``local``'s device."""
+        if not self.live:
+            return local.unsqueeze(0)
+        self.collectives += 1
+        if self.nccl:
+            out = torch.empty((self.world,) + tuple(local.shape), dtype=local.dtype, device=local.device)
+            dist.all_gather_into_tensor(out, local, group=self.group)
+            return out
+        host = local.cpu() if self.stage_host else local
+        out = torch.empty((self.world,) + tuple(host.shape), dtype=host.dtype, device=host.device)
+        dist.all_gather(list(out.unbind(0)), host, group=self.group)
+        return out.to(local.device)
+
+
+def _no_capture(x: Tensor) -> None:
+    if x.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("onset training: a step with synchronised BatchNorm cannot be captured into a HIP graph (its collectives run "
+                           "between the kernels); capture is supported on the single-rank path only")
+
+
+class _BNSyncTrain(torch.autograd.Function):
+    """_BNTrain with the statistics of all ranks: stats kernel -> all_gather(2 C floats) -> merge + apply kernels; backward: sums kernel ->
+    all_gather(2 C floats) -> apply kernel.  dgamma / dbeta are the LOCAL sums (the gradient all-reduce averages them), as in
+    torch.nn.SyncBatchNorm."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, gamma: Tensor, beta: Tensor, res: Optional[Tensor], bn: nn.Module, relu: bool, sg: SyncGroup) -> Tensor:
+        lib = _lib.load()
+        _no_capture(x)
+        rows, ld = x.shape
+        Cc = bn.num_features
+        mine = sg.clips[sg.rank]
+        if rows % mine:
+            raise ValueError(f"synchronised BatchNorm: {rows} rows do not divide into this rank's {mine} clips")
+        rpc = rows // mine
+        if sg.total_rows(rpc) < 2:
+            raise ValueError("synchronised BatchNorm: more than one value per channel is needed over all ranks (as nn.BatchNorm3d in train mode)")
+        track = bn.track_running_stats and bn.running_mean is not None
+        if track and bn.momentum is None:
+            raise NotImplementedError("onset training: BatchNorm3d(momentum=None) (cumulative averaging) is not supported")
+        rm, rv, nbt = (bn.running_mean, bn.running_var, bn.num_batches_tracked) if track else (None, None, None)
+        counts = sg.row_counts(rpc)
+        y = torch.empty_like(x)
+        mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        invstd = torch.empty_like(mean)
+        local = torch.empty(Cc, 2, dtype=torch.float32, device=x.device)
+        ws = _workspace(lib.sf_op_bn_sync_workspace_bytes(rows, Cc), x.device)
+        _lib.check(lib.sf_op_bn_sync_stats(x.data_ptr(), rows, Cc, ld, local.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x)), "sf_op_bn_sync_stats")
+        table = sg.all_gather(local)
+        _lib.check(lib.sf_op_bn_sync_fwd_apply(x.data_ptr(), res.data_ptr() if res is not None else None, rows, Cc, ld, table.data_ptr(), counts.data_ptr(),
+                                               sg.world, gamma.data_ptr(), beta.data_ptr(), float(bn.eps), float(bn.momentum or 0.0),
+                                               rm.data_ptr() if track else None, rv.data_ptr() if track else None, nbt.data_ptr() if track else None,
+                                               int(relu), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x)),
+                   "sf_op_bn_sync_fwd_apply")
+        _bump(rm, rv, nbt)
+        ctx.save_for_backward(x, y if relu else None, gamma, mean, invstd, counts)
+        ctx.has_res = res is not None
+        ctx.Cc, ctx.sg = Cc, sg
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        lib = _lib.load()
+        x, y, gamma, mean, invstd, counts = ctx.saved_tensors
+        sg: SyncGroup = ctx.sg
+        _no_capture(x)
+        rows, ld = x.shape
+        dy = dy.contiguous()
+        need_dx = ctx.needs_input_grad[0]
+        need_dres = ctx.has_res and ctx.needs_input_grad[3]
+        dgamma = torch.empty_like(gamma) if ctx.needs_input_grad[1] else None
+        dbeta = torch.empty_like(gamma) if ctx.needs_input_grad[2] else None
+        local = torch.empty(ctx.Cc, 2, dtype=torch.float32, device=x.device)
+        ws = _workspace(lib.sf_op_bn_sync_workspace_bytes(rows, ctx.Cc), x.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        # the sums and the gather run on every rank whatever this rank needs: the collective count must not depend on it
+        _lib.check(lib.sf_op_bn_sync_bwd_sums(x.data_ptr(), ptr(y), dy.data_ptr(), rows, ctx.Cc, ld, mean.data_ptr(), invstd.data_ptr(), local.data_ptr(),
+                                              ptr(dgamma), ptr(dbeta), ws.data_ptr(), ws.numel(), _stream(x)), "sf_op_bn_sync_bwd_sums")
+        table = sg.all_gather(local)
+        dx = torch.empty_like(x) if need_dx else None
+        dres = torch.empty_like(x) if need_dres else None
+        if dx is not None or dres is not None:
+            _lib.check(lib.sf_op_bn_sync_bwd_apply(x.data_ptr(), ptr(y), dy.data_ptr(), rows, ctx.Cc, ld, table.data_ptr(), counts.data_ptr(), sg.world,
+                                                   gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ptr(dx), ptr(dres), ws.data_ptr(), ws.numel(),
+                                                   _stream(x)), "sf_op_bn_sync_bwd_apply")
+        return dx, dgamma, dbeta, dres, None, None, None
+
+
+def batch_norm_train_sync(x: Tensor, bn: nn.Module, sg: SyncGroup, res: Optional[Tensor] = None, relu: bool = False) -> Tensor:
+    """``batch_norm_train`` with the batch statistics of every rank of ``sg``; updates ``bn``'s running statistics (the same bits on every rank)."""
+    return _BNSyncTrain.apply(x, bn.weight, bn.bias, res, bn, relu, sg)
+
+
+class _SyncState:
+    """Which BatchNorms of one forward run synchronised, and over which group (one SyncGroup, hence one clip-count gather, per group)."""
+
+    def __init__(self, clips: int, device: torch.device, force: bool = False):
+        self.clips, self.device, self.force = clips, device, force
+        self._groups: Dict[object, SyncGroup] = {}
+
+    def group_for(self, bn: nn.Module) -> Optional[SyncGroup]:
+        """torch.nn.SyncBatchNorm's own rule: an nn.SyncBatchNorm module, an initialised process group (the module's, else the default one) and
+        more than one rank.  Everything else -- a converted net without a process group or in a world of one included -- takes the plain path."""
+        live = dist.is_available() and dist.is_initialized()
+        group = None
+        if not self.force:
+            if not isinstance(bn, nn.SyncBatchNorm) or not live:
+                return None
+            group = bn.process_group
+            if dist.get_world_size(group) < 2:
+                return None
+        elif live and isinstance(bn, nn.SyncBatchNorm):
+            group = bn.process_group
+        sg = self._groups.get(group)
+        if sg is None:
+            sg = self._groups[group] = SyncGroup(group, self.clips, self.device)
+        return sg
+
+
 class _Pool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, NT: int, HW: int, Cc: int) -> Tensor:
@@ -199,18 +366,21 @@ def frames_to_rows(x: Tensor, ld: int = 4) -> Tensor:
 class _Act:
     """A channels-last activation and its geometry."""
 
-    def __init__(self, rows: Tensor, N: int, T: int, H: int, W: int):
-        self.rows, self.N, self.T, self.H, self.W = rows, N, T, H, W
+    def __init__(self, rows: Tensor, N: int, T: int, H: int, W: int, sync: Optional[_SyncState] = None):
+        self.rows, self.N, self.T, self.H, self.W, self.sync = rows, N, T, H, W, sync
 
 
 def _conv(conv: nn.Conv3d, a: _Act) -> _Act:
     geo = conv_geometry(conv, a.N, a.T, a.H, a.W, cin_ld=a.rows.shape[1])
     Ho, Wo = geo.out_hw
-    return _Act(vconv(a.rows, conv.weight, geo), a.N, a.T, Ho, Wo)
+    return _Act(vconv(a.rows, conv.weight, geo), a.N, a.T, Ho, Wo, a.sync)
 
 
 def _bn(bn: nn.BatchNorm3d, a: _Act, res: Optional[_Act] = None, relu: bool = True) -> _Act:
-    return _Act(batch_norm_train(a.rows, bn, res.rows if res is not None else None, relu), a.N, a.T, a.H, a.W)
+    r = res.rows if res is not None else None
+    sg = a.sync.group_for(bn) if a.sync is not None else None
+    rows = batch_norm_train(a.rows, bn, r, relu) if sg is None else batch_norm_train_sync(a.rows, bn, sg, r, relu)
+    return _Act(rows, a.N, a.T, a.H, a.W, a.sync)
 
 
 def _basic_block(blk: nn.Module, a: _Act) -> _Act:
@@ -226,11 +396,23 @@ def _basic_block(blk: nn.Module, a: _Act) -> _Act:
     return _bn(c2[1], out, res=res, relu=True)
 
 
-def onset_train_forward(net: nn.Module, x: Tensor) -> Tensor:
-    """VideoOnsetNet.forward in train mode with an autograd graph onto every parameter: (N, 3, T, H, W) -> (N, T) logits."""
+def onset_train_forward(net: nn.Module, x: Tensor, _force_sync: bool = False) -> Tensor:
+    """VideoOnsetNet.forward in train mode with an autograd graph onto every parameter: (N, 3, T, H, W) -> (N, T) logits.
+
+    A net converted by ``torch.nn.SyncBatchNorm.convert_sync_batchnorm`` normalises with the statistics of every rank's clips when a process
+    group of more than one rank is initialised (ranks may hold different clip counts, none zero); average the gradients afterwards
+    (``syncfusion_amd.allreduce_gradients``).  ``_force_sync`` (tests, tools) sends every BatchNorm through the split-phase kernels whatever
+    the module type and the world size."""
     N, _, T, H, W = x.shape
     trunk = net.net.model
-    a = _Act(frames_to_rows(x), N, T, H, W)
+    # without a process group (and unforced) no module can take the synchronised path: the step is today's, with nothing added per layer
+    sync = _SyncState(N, x.device, _force_sync) if _force_sync or (dist.is_available() and dist.is_initialized()) else None
+    if N == 0:
+        # a rank whose shard is empty still joins the clip-count gather, so that EVERY rank of the group raises instead of waiting for it
+        if sync is not None:
+            sync.group_for(trunk.stem[1])
+        raise ValueError("onset training: empty batch (0 clips)")
+    a = _Act(frames_to_rows(x), N, T, H, W, sync)
     st = trunk.stem   # main/resnet.py:181-192
     a = _bn(st[1], _conv(st[0], a))
     a = _bn(st[4], _conv(st[3], a))

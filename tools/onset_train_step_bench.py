@@ -5,7 +5,11 @@ syncfusion_amd/onset_training.py) and, in the same run, the same step on torch's
 Device events around `--steps` steps after `--warmup` steps; FLOPs per step = 3 x the forward's convolutions (forward, data and weight
 gradients; the stem has no data gradient, so this slightly overstates the work); peak memory from torch.cuda.max_memory_allocated.
 
-    python tools/onset_train_step_bench.py [--batch 16] [--steps 5] [--warmup 2] [--skip-torch]
+    python tools/onset_train_step_bench.py [--batch 16] [--steps 5] [--warmup 2] [--skip-torch] [--split-phase [--rccl]]
+
+`--split-phase` adds a leg that sends every BatchNorm through the cross-rank kernels (sf_op_bn_sync_*) at world size 1: the price of the extra
+launches of data-parallel training with no link cost in it.  With `--rccl` a one-rank nccl process group carries the 2 x 37 gathers (RCCL
+on device tensors); without it the "gather" is a reshape.
 """
 from __future__ import annotations
 
@@ -65,6 +69,9 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--skip-torch", action="store_true")
+    ap.add_argument("--split-phase", action="store_true", help="also time the step with every BatchNorm on the split-phase (cross-rank) kernels")
+    ap.add_argument("--rccl", action="store_true", help="with --split-phase: a one-rank nccl group carries the gathers")
+    ap.add_argument("--master-port", type=int, default=29671)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -79,6 +86,26 @@ def main():
     ms, gib = time_steps(model, net, batch, a.steps, a.warmup)
     out["hip"] = {"ms_per_step": round(ms, 2), "tflops": round(step_flop / ms / 1e9, 2), "peak_gib": round(gib, 2)}
     print(f"HIP path    : {ms:8.2f} ms/step  {step_flop / ms / 1e9:6.2f} TFLOP/s  peak {gib:6.2f} GiB", flush=True)
+    if a.split_phase:
+        from syncfusion_amd.onset_training import onset_train_forward
+
+        if a.rccl:
+            import torch.distributed as dist
+
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            os.environ.setdefault("MASTER_PORT", str(a.master_port))
+            dist.init_process_group("nccl", rank=0, world_size=1)
+        del model, net
+        torch.cuda.empty_cache()
+        net = torch.nn.SyncBatchNorm.convert_sync_batchnorm(VideoOnsetNet(False)).to(dev).train()
+        model = OnsetModel(1e-4, 0.9, 0.999, 1e-8, 1e-2, net).to(dev)
+        ms_s, gib_s = time_steps(model, lambda x: onset_train_forward(net, x, _force_sync=True), batch, a.steps, a.warmup)
+        out["hip_split_phase"] = {"ms_per_step": round(ms_s, 2), "tflops": round(step_flop / ms_s / 1e9, 2), "peak_gib": round(gib_s, 2),
+                                  "gathers": "rccl, one rank" if a.rccl else "none (reshape)"}
+        print(f"HIP split-phase ({out['hip_split_phase']['gathers']}): {ms_s:8.2f} ms/step  {step_flop / ms_s / 1e9:6.2f} TFLOP/s  peak {gib_s:6.2f} GiB",
+              flush=True)
+        if a.rccl:
+            dist.destroy_process_group()
     if not a.skip_torch:
         del model, net
         torch.cuda.empty_cache()
