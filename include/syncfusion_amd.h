@@ -228,7 +228,32 @@ int sf_resampler_forward(sf_resampler *h, const float *x, int R, int L, float *o
  *     frames:(N,T,H,W,3) uint8 device memory -> out:(N,3,T,out_h,out_w) fp32; mean3 / std3 are HOST arrays of 3 floats.
  *   sf_times_to_track replaces the impulse-track construction of main/dataset_diffusion.py:58-72
  *     (`onset[:, int(t * sr)] = 1.0`): times:(n_times) float64 seconds and clip_of:(n_times) clip indices, device memory.
+ *   sf_frames_augment replaces the TRAINING transform of the onset data, cfg/data/data-onset-greatesthit-augment.yaml:8-28 as
+ *     main/dataset_onset.py:152-165 applies it to the (T,C,H,W) stack of one clip (variants: main/datamodule_onset.py:138-156):
+ *     ToTensor -> Resize((resize_h, resize_w), antialias=True) -> RandomCrop / CenterCrop((out_h, out_w)) -> ColorJitter -> Normalize ->
+ *     (C,T,H,W), torchvision 0.14.1 semantics for float tensors, for a batch of clips with per-clip parameters:
+ *     frames:(N,T,H,W,3) uint8 device memory -> out:(N,3,T,out_h,out_w) fp32.  The resized image is never materialised: the antialiased
+ *     filter (scale = in / resized) is evaluated at the pixels that survive the crop.  The random draws stay with the caller: one
+ *     sf_augment_clip per clip -- crop origin in the resized image, the order of the four colour operations (0 brightness, 1 contrast,
+ *     2 saturation, 3 hue: ColorJitter.forward's fn_idx), one factor per operation and a presence mask (bit op set: applied; an absent
+ *     operation is skipped, not applied with a neutral factor).  table_host is validated HERE, before anything is launched (crop inside
+ *     the resized image, order a permutation, finite factors, brightness / contrast / saturation >= 0, |hue| <= 0.5); table_dev is the
+ *     caller's device copy of the same N entries, which the kernels read.  Contrast blends with the mean gray of one frame's cropped
+ *     pixels AFTER the operations before it, so a clip with contrast takes two passes (the second in place on `out`); the per-frame sums
+ *     are reduced in a fixed order without atomics: equal inputs give equal bits.  ws: sf_frames_augment_workspace_bytes() bytes of
+ *     device scratch.  mean3 / std3 are HOST arrays of 3 floats.
  * ---------------------------------------------------------------------------------------- */
+typedef struct sf_augment_clip {
+  int32_t top, left;
+  int32_t order[4];
+  float factor[4];
+  int32_t mask;
+  int32_t reserved;
+} sf_augment_clip;
+int64_t sf_frames_augment_workspace_bytes(int N, int T, int out_h, int out_w);
+int sf_frames_augment(const uint8_t *frames, int N, int T, int H, int W, int resize_h, int resize_w, int out_h, int out_w,
+                      const sf_augment_clip *table_host, const sf_augment_clip *table_dev, const float *mean3, const float *std3, float *out,
+                      void *ws, int64_t ws_bytes, void *stream);
 int sf_frames_preprocess(const uint8_t *frames, int N, int T, int H, int W, int out_h, int out_w, const float *mean3, const float *std3,
                          float *out, void *stream);
 int sf_times_to_track(const double *times, const int32_t *clip_of, int n_times, double sample_rate, int B, int L, float *track, void *stream);

@@ -6,8 +6,8 @@ Public surface = the reference's own: ``DiffusionModel`` 
 runs in ``lib/libsyncfusion_amd.so`` (hand-written HIP, C ABI in include/syncfusion_amd.h).
 """
 from . import _lib  # noqa: F401
-from . import autograd, onset_training, shards, training, video_chunks  # noqa: F401
-from .config import instantiate, instantiate_model_yaml
+from . import autograd, frame_transforms, onset_training, shards, training, video_chunks  # noqa: F401
+from .config import instantiate, instantiate_class, instantiate_frames_transforms, instantiate_model_yaml
 from .diffusion import DiffusionModel, LinearSchedule, UNetV0, VDiffusion, VSampler
 from .encoder1d import Encoder1d
 from .generation import generate_batch, generate_dataset
@@ -20,5 +20,5 @@ from .training import allreduce_gradients
 
 __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule", "Encoder1d", "VideoOnsetNet", "Model", "OnsetModel",
            "RandomEmbedder", "generate_batch", "generate_dataset", "instantiate", "instantiate_model_yaml", "onsets_to_track", "cut_prefix_crop", "resample",
-           "allreduce_gradients"]
+           "allreduce_gradients", "frame_transforms", "instantiate_class", "instantiate_frames_transforms"]
 __version__ = "0.1.0"

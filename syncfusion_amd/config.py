@@ -25,6 +25,13 @@ TARGET_MAP = {
     "audio_encoders_pytorch.Encoder1d": "syncfusion_amd.encoder1d.Encoder1d",
     "laion_clap.CLAP_Module": "syncfusion_amd.module.RandomEmbedder",  # CLAP is out of scope: offline stub
     "main.onset_net.VideoOnsetNet": "syncfusion_amd.onset_net.VideoOnsetNet",
+    # the onset data's frame transforms (cfg/data/data-onset-greatesthit-augment.yaml:8-52): descriptions of one device pass
+    "torchvision.transforms.Compose": "syncfusion_amd.frame_transforms.Compose",
+    "torchvision.transforms.Resize": "syncfusion_amd.frame_transforms.Resize",
+    "torchvision.transforms.RandomCrop": "syncfusion_amd.frame_transforms.RandomCrop",
+    "torchvision.transforms.CenterCrop": "syncfusion_amd.frame_transforms.CenterCrop",
+    "torchvision.transforms.ColorJitter": "syncfusion_amd.frame_transforms.ColorJitter",
+    "torchvision.transforms.Normalize": "syncfusion_amd.frame_transforms.Normalize",
 }
 
 
@@ -53,6 +60,32 @@ def instantiate(node: Any, **overrides) -> Any:
     if node.get("_partial_", False):
         return functools.partial(fn, **kwargs)
     return fn(**kwargs)
+
+
+def instantiate_class(node: Any) -> Any:
+    """The LightningCLI / jsonargparse form the reference's cfg/ files use: a dict with ``class_path`` and ``init_args`` becomes
+    ``class_path(**init_args)``, recursively (lists and plain dicts are walked, everything else passes through)."""
+    if isinstance(node, list):
+        return [instantiate_class(v) for v in node]
+    if isinstance(node, str) and _FLOAT.match(node):
+        return float(node)
+    if not isinstance(node, dict):
+        return node
+    if "class_path" not in node:
+        return {k: instantiate_class(v) for k, v in node.items()}
+    extra = set(node) - {"class_path", "init_args"}
+    if extra:
+        raise ValueError(f"{node['class_path']}: unexpected keys {sorted(extra)} next to class_path / init_args")
+    kwargs = {k: instantiate_class(v) for k, v in (node.get("init_args") or {}).items()}
+    return _locate(node["class_path"])(**kwargs)
+
+
+def instantiate_frames_transforms(node: Any):
+    """One ``*_frames_transforms`` block of the onset data YAML -> a ``frame_transforms.Compose``; ``null`` selects the dataset's default
+    chain (main/dataset_onset.py:44-50)."""
+    from . import frame_transforms
+
+    return frame_transforms.default_chain() if node is None else instantiate_class(node)
 
 
 def load_yaml(path: str) -> Dict[str, Any]:

@@ -84,6 +84,50 @@ int sf_frames_preprocess(const uint8_t *frames, int N, int T, int H, int W, int 
   SF_API_END
 }
 
+int64_t sf_frames_augment_workspace_bytes(int N, int T, int out_h, int out_w) {
+  if (N < 1 || T < 1 || out_h < 1 || out_w < 1) return -1;
+  return frames_augment_workspace_bytes(N, T, out_h, out_w);
+}
+
+static_assert(sizeof(sf_augment_clip) == sizeof(AugClip) && sizeof(AugClip) == 48, "sf_augment_clip is the kernels' table entry");
+int sf_frames_augment(const uint8_t *frames, int N, int T, int H, int W, int resize_h, int resize_w, int out_h, int out_w,
+                      const sf_augment_clip *table_host, const sf_augment_clip *table_dev, const float *mean3, const float *std3, float *out, void *ws,
+                      int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!frames || !out || !mean3 || !std3 || !table_host || !table_dev || N < 1 || T < 1 || H < 1 || W < 1 || resize_h < 1 || resize_w < 1 ||
+      out_h < 1 || out_w < 1)
+    fail(SF_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 3; ++i)
+    if (!(std3[i] > 0.f)) fail(SF_ERR_INVALID, "std must be positive");
+  if (out_h > resize_h || out_w > resize_w)
+    fail(SF_ERR_INVALID, "crop (%d, %d) larger than the resized frame (%d, %d)", out_h, out_w, resize_h, resize_w);
+  bool any_contrast = false;
+  for (int n = 0; n < N; ++n) {   // every way a table could send a kernel out of bounds (or into NaN) is refused here
+    const sf_augment_clip &c = table_host[n];
+    if (c.top < 0 || c.left < 0 || c.top > resize_h - out_h || c.left > resize_w - out_w)
+      fail(SF_ERR_INVALID, "clip %d: crop origin (%d, %d) + (%d, %d) lies outside the resized frame (%d, %d)", n, c.top, c.left, out_h, out_w, resize_h,
+           resize_w);
+    int seen = 0;
+    for (int k = 0; k < 4; ++k)
+      if (c.order[k] >= 0 && c.order[k] < 4) seen |= 1 << c.order[k];
+    if (seen != 15) fail(SF_ERR_INVALID, "clip %d: order (%d, %d, %d, %d) is not a permutation of 0..3", n, c.order[0], c.order[1], c.order[2], c.order[3]);
+    if (c.mask < 0 || c.mask > 15) fail(SF_ERR_INVALID, "clip %d: mask %d outside 0..15", n, c.mask);
+    for (int k = 0; k < 4; ++k) {
+      if (!std::isfinite(c.factor[k])) fail(SF_ERR_INVALID, "clip %d: factor %d is not finite", n, k);
+      if (k < 3 ? c.factor[k] < 0.f : std::fabs(c.factor[k]) > 0.5f) fail(SF_ERR_INVALID, "clip %d: factor %d = %g outside its range", n, k, (double)c.factor[k]);
+    }
+    any_contrast = any_contrast || (c.mask & 2);
+  }
+  const int64_t need = frames_augment_workspace_bytes(N, T, out_h, out_w);
+  if (!ws || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  hipError_t e = launch_frames_augment(frames, N, T, H, W, resize_h, resize_w, out_h, out_w, reinterpret_cast<const AugClip *>(table_dev), any_contrast, mean3,
+                                       std3, out, static_cast<float *>(ws), static_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) fail(SF_ERR_UNSUPPORTED, "down-scaling factor above 7.5 (or more than 2^31 workgroups) is not supported");
+  SF_HIP(e);
+  return SF_OK;
+  SF_API_END
+}
+
 int sf_times_to_track(const double *times, const int32_t *clip_of, int n_times, double sample_rate, int B, int L, float *track, void *stream) {
   SF_API_BEGIN
   if (!track || B < 1 || L < 1 || n_times < 0 || (n_times > 0 && (!times || !clip_of)) || !(sample_rate > 0)) fail(SF_ERR_INVALID, "bad argument");

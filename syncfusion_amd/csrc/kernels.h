@@ -387,6 +387,19 @@ hipError_t launch_conv_sp(int dt, const void *in, int in_ld, const void *wfr, co
 // uint8 RGB frames (N, T, H, W, 3) -> (N, 3, T, oh, ow) fp32: /255, antialiased bilinear resize (ATen semantics), (x - mean) / std
 hipError_t launch_frames_preprocess(const unsigned char *frames, int N, int T, int H, int W, int oh, int ow, const float *mean, const float *stdv,
                                     float *out, hipStream_t s);
+// The training transforms of the onset data (cfg/data/data-onset-greatesthit-augment.yaml:8-28): Resize((rh, rw), antialias) -> crop
+// (top, left, oh, ow) -> ColorJitter -> Normalize -> (N, 3, T, oh, ow), per-clip parameters in a device table (= sf_augment_clip).
+// part: N * T * ceil(oh * ow / 256) floats of scratch (per-frame gray partials of the contrast mean); any_contrast = false skips pass B.
+struct AugClip {
+  int top, left;
+  int order[4];      // a permutation of 0..3: 0 brightness, 1 contrast, 2 saturation, 3 hue
+  float factor[4];   // indexed by operation
+  int mask;          // bit op: the operation is present
+  int reserved;
+};
+int64_t frames_augment_workspace_bytes(int N, int T, int oh, int ow);
+hipError_t launch_frames_augment(const unsigned char *frames, int N, int T, int H, int W, int rh, int rw, int oh, int ow, const AugClip *table_dev,
+                                 bool any_contrast, const float *mean, const float *stdv, float *out, float *part, hipStream_t s);
 // track (B, L) = 0 except track[clip_of[i]][int(times[i] * sample_rate)] = 1
 hipError_t launch_times_to_track(const double *times, const int *clip_of, int n_times, double sample_rate, int B, int L, float *track, hipStream_t s);
 

@@ -69,17 +69,42 @@ def read_frames_u8(paths: Sequence[str], pin: bool = True) -> Tensor:
     return t.pin_memory() if pin and torch.cuda.is_available() else t
 
 
-def chunk_clip(chunk: dict, device, frame_file_suffix: str = ".jpg", size: Tuple[int, int] = (112, 112)) -> Tensor:
-    """Frames of one chunk -> ``(3, T, 112, 112)`` float32 on ``device``: main/dataset_onset.py:121-165 (``__getitem__`` +
-    ``read_image_and_apply_transforms``) with the transform chain in one HIP pass."""
+def chunk_frames_u8(chunk: dict, frame_file_suffix: str = ".jpg", pin: bool = True) -> Tensor:
+    """The decoded frames of one chunk, ``(T, H, W, 3)`` uint8 on the host (main/dataset_onset.py:121-134)."""
     frames = natural_sorted(glob.glob(f"{chunk['frames_path']}/*{frame_file_suffix}"))[chunk["start_frame"]: chunk["end_frame"]]
-    u8 = read_frames_u8(frames).to(device, non_blocking=True)
+    return read_frames_u8(frames, pin)
+
+
+def chunk_clip(chunk: dict, device, frame_file_suffix: str = ".jpg", size: Tuple[int, int] = (112, 112), frames_transforms=None,
+               generator: Optional[torch.Generator] = None) -> Tensor:
+    """Frames of one chunk -> ``(3, T, 112, 112)`` float32 on ``device``: main/dataset_onset.py:121-165 (``__getitem__`` +
+    ``read_image_and_apply_transforms``) with the transform chain in one HIP pass.  ``frames_transforms``: a
+    ``frame_transforms.Compose`` (the dataset's ``frames_transforms`` argument) instead of the default evaluation chain."""
+    u8 = chunk_frames_u8(chunk, frame_file_suffix).to(device, non_blocking=True)
+    if frames_transforms is not None:
+        return frames_transforms(u8[None], generator=generator)[0]
     return frames_to_clip(u8[None], size)[0]
 
 
-def iter_clips(chunks: Sequence[dict], batch_size: int, device, frame_file_suffix: str = ".jpg") -> Iterator[Tuple[Tensor, Tensor, List[dict]]]:
-    """Batches ``(frames (N, 3, T, 112, 112), labels (N, T), chunk dicts)`` as the reference's DataLoader stacks them."""
-    for i in range(0, len(chunks), batch_size):
-        part = list(chunks[i: i + batch_size])
-        clips = torch.stack([chunk_clip(c, device, frame_file_suffix) for c in part])
+def iter_clips(chunks: Sequence[dict], batch_size: int, device, frame_file_suffix: str = ".jpg", frames_transforms=None, shuffle: bool = False,
+               drop_last: bool = False, generator: Optional[torch.Generator] = None) -> Iterator[Tuple[Tensor, Tensor, List[dict]]]:
+    """Batches ``(frames (N, 3, T, 112, 112), labels (N, T), chunk dicts)`` as the reference's DataLoader stacks them.
+    ``shuffle`` / ``drop_last`` are what ``train_dataloader`` sets (main/datamodule_onset.py:104-112); the permutation is drawn from
+    ``generator`` before the first batch.  With ``frames_transforms`` the frames of a whole batch are decoded, uploaded once and
+    transformed in one launch sequence, the random parameters of its clips drawn from ``generator`` in batch order."""
+    idx = torch.randperm(len(chunks), generator=generator).tolist() if shuffle else list(range(len(chunks)))
+    for i in range(0, len(idx), batch_size):
+        part = [chunks[j] for j in idx[i: i + batch_size]]
+        if drop_last and len(part) < batch_size:
+            break
+        if frames_transforms is None:
+            clips = torch.stack([chunk_clip(c, device, frame_file_suffix) for c in part])
+        else:
+            frames = [chunk_frames_u8(c, frame_file_suffix, pin=False) for c in part]
+            if any(f.shape != frames[0].shape for f in frames):
+                raise ValueError("chunks of one batch differ in frame count or frame size")
+            u8 = torch.stack(frames)
+            if torch.cuda.is_available():
+                u8 = u8.pin_memory()
+            clips = frames_transforms(u8.to(device, non_blocking=True), generator=generator)
         yield clips, torch.stack([c["labels"] for c in part]).to(device), part
