@@ -191,6 +191,21 @@ int sf_onsetnet_forward(sf_onsetnet *h, const float *frames, int N, int T, int H
 int sf_onsetnet_debug_enable(sf_onsetnet *h, float *buf, int64_t cap_floats);
 int sf_onsetnet_debug_count(const sf_onsetnet *h);
 int sf_onsetnet_debug_info(const sf_onsetnet *h, int i, char *name_out, int name_cap, int64_t *offset, int64_t *rows, int32_t *cols);
+/* Detail mode of the debug taps (tests only).  With enable != 0 every later forward with a debug buffer records, besides the five stage
+ * taps (stem, layer1 .. layer4), the output of each of the 37 convolutions as (rows, cout) fp32, named after the convolution's
+ * state_dict prefix without "net.model.": stem.0, stem.3, layerL.B.conv1.0.0, layerL.B.conv1.0.3, layerL.B.conv2.0.0, layerL.B.conv2.0.3
+ * and layerL.0.downsample.0 (L = 2, 3, 4).  Rows are ordered ((n T + t) H + h) W + w, so a clip is one contiguous row range: with
+ * n_clips > 0 every tap of such a forward, the stage taps included, holds only the rows of clips[0 .. n_clips) (host array of clip
+ * indices, copied by the call), back to back in that order; n_clips == 0 keeps all clips.  enable == 0 restores the five stage taps over
+ * all clips.  The taps are copies made after a convolution's launches: the dispatch and the logits do not depend on the mode. */
+int sf_onsetnet_debug_detail(sf_onsetnet *h, int enable, const int32_t *clips, int n_clips);
+/* The launch sequence behind tap i of the last forward (-1: no such tap; stage taps report 0). */
+#define SF_ONSET_PATH_GEMM 0       /* one conv_gemm launch (generic / macro-tile implicit GEMM) */
+#define SF_ONSET_PATH_GEMM_SPLIT 1 /* two conv_gemm launches: whole 192-column tiles, then the remaining columns */
+#define SF_ONSET_PATH_SP 2         /* frame-walk (1,3,3) kernel (conv_sp.hip) */
+#define SF_ONSET_PATH_TW 3         /* temporal-walk (3,1,1) kernel (conv_tw.hip) */
+#define SF_ONSET_PATH_STEM 4       /* RGB (1,7,7) stride-2 stem kernel (onset_stem.hip) */
+int sf_onsetnet_debug_path(const sf_onsetnet *h, int i);
 
 /* ------------------------------------------------------------------------------------------
  * Onset glue on device: logits -> one-hot impulse track

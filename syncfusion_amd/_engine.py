@@ -328,8 +328,20 @@ class OnsetNetEngine(_Base):
     def stale(self, net: torch.nn.Module) -> bool:
         return self.version.changed(net) or getattr(net, "compute_dtype", self.dtype) != self.dtype
 
-    def forward(self, x: torch.Tensor, taps: Optional[dict] = None, cap_floats: int = 1 << 27) -> torch.Tensor:
+    # sf_onsetnet_debug_path codes (include/syncfusion_amd.h, SF_ONSET_PATH_*)
+    PATHS = ("conv_gemm", "conv_gemm_split", "conv_sp", "conv_tw", "onset_stem")
+
+    def forward(self, x: torch.Tensor, taps: Optional[dict] = None, cap_floats: int = 1 << 27, detail: bool = False,
+                clips: Optional[Sequence[int]] = None, paths: Optional[dict] = None) -> torch.Tensor:
+        """taps (tests only): filled with the five stage outputs as (rows, C) fp32; with detail=True also with the output of each of
+        the 37 convolutions under its state_dict prefix ("stem.0", "layer2.0.conv1.0.3", "layer2.0.downsample.0", ...), every tap
+        restricted to the rows of `clips` (in that order; None = all clips), from a tap buffer filled with NaN before the forward.
+        paths: filled with tap name -> PATHS entry, the launch sequence that produced it."""
         N, _, T, H, W = x.shape
+        if (detail or clips is not None or paths is not None) and taps is None:
+            raise ValueError("detail / clips / paths need a taps dict")
+        if clips is not None and not detail:
+            raise ValueError("clips restrict the detail taps: pass detail=True")
         with torch.cuda.device(self.device):
             xs = _lib.f32c(x)
             out = torch.empty(N, T, dtype=torch.float32, device=self.device)
@@ -339,7 +351,12 @@ class OnsetNetEngine(_Base):
             ws = self._workspace(n, self.device)
             buf = None
             if taps is not None:
-                buf = torch.empty(cap_floats, dtype=torch.float32, device=self.device)
+                if detail:
+                    buf = torch.full((cap_floats,), float("nan"), dtype=torch.float32, device=self.device)
+                    sel = (C.c_int32 * len(clips))(*clips) if clips else None
+                    check(self.lib.sf_onsetnet_debug_detail(self.handle, 1, sel, len(clips) if clips else 0), "debug_detail")
+                else:
+                    buf = torch.empty(cap_floats, dtype=torch.float32, device=self.device)
                 check(self.lib.sf_onsetnet_debug_enable(self.handle, buf.data_ptr(), buf.numel()), "debug_enable")
             try:
                 check(self.lib.sf_onsetnet_forward(self.handle, xs.data_ptr(), N, T, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -351,7 +368,11 @@ class OnsetNetEngine(_Base):
                         off, rows, cols = C.c_int64(), C.c_int64(), C.c_int32()
                         check(self.lib.sf_onsetnet_debug_info(self.handle, i, name, 128, C.byref(off), C.byref(rows), C.byref(cols)), "debug_info")
                         taps[name.value.decode()] = buf[off.value: off.value + rows.value * cols.value].reshape(rows.value, cols.value).clone()
+                        if paths is not None:
+                            paths[name.value.decode()] = self.PATHS[self.lib.sf_onsetnet_debug_path(self.handle, i)]
             finally:
                 if taps is not None:
                     self.lib.sf_onsetnet_debug_enable(self.handle, None, 0)
+                    if detail:
+                        self.lib.sf_onsetnet_debug_detail(self.handle, 0, None, 0)
         return out

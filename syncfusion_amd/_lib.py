@@ -89,6 +89,8 @@ SYMBOLS = {
     "sf_onsetnet_forward": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _L, _P]),
     "sf_onsetnet_debug_enable": (_I, [_P, _P, _L]),
     "sf_onsetnet_debug_count": (_I, [_P]),
+    "sf_onsetnet_debug_detail": (_I, [_P, _I, C.POINTER(C.c_int32), _I]),
+    "sf_onsetnet_debug_path": (_I, [_P, _I]),
     "sf_onsetnet_debug_info": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_L), C.POINTER(_L), C.POINTER(C.c_int32)]),
     "sf_onsets_to_track": (_I, [_P, _I, _I, _P, _F, _F, _F, _P, _I, _P]),
     "sf_frames_preprocess": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

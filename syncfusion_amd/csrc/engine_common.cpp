@@ -112,4 +112,24 @@ void DebugTaps::tap(const std::string &name, int dt, const void *x, int ld, int6
   used += n;
 }
 
+void DebugTaps::tap_clips(const std::string &name, int dt, const void *x, int ld, int64_t rows_per_clip, int n_clips, int cols, int path,
+                          hipStream_t s) {
+  if (!buf) return;
+  if (clips.empty()) {
+    tap(name, dt, x, ld, rows_per_clip * n_clips, cols, s);
+    entries.back().path = path;
+    return;
+  }
+  const int64_t per = rows_per_clip * cols, n = per * (int64_t)clips.size();
+  if (used + n > cap) fail(SF_ERR_WORKSPACE, "debug buffer too small at tap '%s'", name.c_str());
+  int64_t at = used;
+  for (int c : clips) {
+    if (c < 0 || c >= n_clips) fail(SF_ERR_INVALID, "debug clip %d outside the batch of %d", c, n_clips);
+    SF_HIP(launch_to_f32(dt, static_cast<const char *>(x) + (size_t)c * rows_per_clip * ld * dsize(dt), ld, rows_per_clip, cols, buf + at, s));
+    at += per;
+  }
+  entries.push_back({name, used, rows_per_clip * (int64_t)clips.size(), cols, path});
+  used += n;
+}
+
 }  // namespace sf

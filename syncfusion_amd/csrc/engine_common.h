@@ -87,14 +87,20 @@ struct DebugTaps {
     std::string name;
     int64_t offset, rows;
     int cols;
+    int path = 0;   // which launch sequence produced the tensor (engine-defined; sf_onsetnet_debug_path)
   };
   std::vector<Entry> entries;
+  bool detail = false;      // onset engine: also tap the output of every convolution (sf_onsetnet_debug_detail)
+  std::vector<int> clips;   // onset engine, detail mode: the clips whose rows are copied, in this order (empty = all)
   void reset() {
     used = 0;
     entries.clear();
   }
   // copies rows x cols of a DT activation (row stride ld) as fp32
   void tap(const std::string &name, int dt, const void *x, int ld, int64_t rows, int cols, hipStream_t s);
+  // the same for an activation of n_clips x rows_per_clip rows, restricted to `clips` when that list is not empty: one entry, the
+  // chosen clips' row ranges back to back
+  void tap_clips(const std::string &name, int dt, const void *x, int ld, int64_t rows_per_clip, int n_clips, int cols, int path, hipStream_t s);
 };
 
 // One packed convolution / linear layer.

@@ -18,6 +18,7 @@ using namespace sf;
 namespace {
 
 struct Conv3 {
+  std::string name;      // state-dict prefix of the convolution without "net.model." (the name of its detail tap)
   ConvW w;
   void *wsp = nullptr;   // (1,3,3) stride-1 convolutions of 64 channels: weights in the frame-walk kernel's fragment order (conv_sp.hip)
   void *wtw = nullptr;   // (3,1,1) convolutions with 64 outputs: weights in the temporal-walk kernel's fragment order (conv_tw.hip)
@@ -54,6 +55,7 @@ int midplanes(int in, int planes) { return (in * planes * 27) / (in * 9 + 3 * pl
 Conv3 make_conv(sf_onsetnet &o, Packer &pk, const std::string &conv_name, const std::string &bn_name, int cin, int cout, int kt,
                 int kh, int kw, int sh, int pt, int ph, int cin_ld = 0, int cout_ld = 0) {
   Conv3 c;
+  c.name = conv_name.compare(0, 10, "net.model.") == 0 ? conv_name.substr(10) : conv_name;
   c.cin_real = cin;
   c.cout = cout;
   // multiples of 64 so that every layer but the RGB stem runs on the main (v2) MFMA kernel
@@ -122,15 +124,28 @@ struct OnsetExec {
   OnsetPlan &p;
   hipStream_t s;
 
+  // Debug taps are copies made after the launches; without a debug buffer (every production call) they do nothing.  Stage taps are
+  // always recorded, the per-convolution ones in detail mode only.
+  void tap(const std::string &name, const void *x, int ld, int Ho, int Wo, int cols, int path, bool stage) {
+    if (!o.dbg.buf || (!stage && !o.dbg.detail)) return;
+    o.dbg.tap_clips(name, o.dt, x, ld, (int64_t)p.T * Ho * Wo, p.N, cols, path, s);
+  }
+
   void conv(const Conv3 &c, const void *in, int Hi, int Wi, void *out, int &Ho, int &Wo, const void *res, bool relu) {
+    const int path = launch(c, in, Hi, Wi, out, Ho, Wo, res, relu);
+    tap(c.name, out, c.cout_ld, Ho, Wo, c.cout, path, false);
+  }
+
+  // returns the SF_ONSET_PATH_* code of the launch sequence that ran
+  int launch(const Conv3 &c, const void *in, int Hi, int Wi, void *out, int &Ho, int &Wo, const void *res, bool relu) {
     out_hw(Hi, Wi, c, Ho, Wo);
     if (c.wsp && !res) {   // layer-1 spatial convolution: frame walk, register-stationary weights, one halo tile per frame
       SF_HIP(launch_conv_sp(o.dt, in, c.cin_ld, c.wsp, c.w.bias, c.cout, out, c.cout_ld, p.N, p.T, Hi, Wi, relu ? 1 : 0, s));
-      return;
+      return SF_ONSET_PATH_SP;
     }
     if (c.wtw) {   // wide-spatial temporal convolution: frame walk with a three-frame LDS ring (each mid row fetched once, not three times)
       SF_HIP(launch_conv_tw(o.dt, in, c.cin_ld, c.cin_real, c.wtw, c.w.bias, res, c.cout_ld, out, c.cout_ld, p.N, p.T, Ho * Wo, relu ? 1 : 0, s));
-      return;
+      return SF_ONSET_PATH_TW;
     }
     ConvGemmArgs a;
     a.geom = 1;
@@ -180,9 +195,10 @@ struct OnsetExec {
       a2.res = res ? static_cast<const char *>(res) + (size_t)192 * q192 * es : nullptr;
       SF_HIP(launch_conv_gemm(o.dt, a1, s));
       SF_HIP(launch_conv_gemm(o.dt, a2, s));
-      return;
+      return SF_ONSET_PATH_GEMM_SPLIT;
     }
     SF_HIP(launch_conv_gemm(o.dt, a, s));
+    return SF_ONSET_PATH_GEMM;
   }
 };
 
@@ -278,11 +294,12 @@ int sf_onsetnet_forward(sf_onsetnet *h, const float *frames, int N, int T, int H
   if (h->stem_wk && h->stem_s.cin_ld == 4 && h->stem_s.cout_ld == 64 && (int64_t)N * T * H * W * 8 < 0x7FFFFFF0ll) {
     out_hw(H, W, h->stem_s, hh, ww);
     SF_HIP(launch_onset_stem(h->dt, p.in, N * T, H, W, h->stem_wk, h->stem_s.w.bias, h->stem_s.cout, M, h->stem_s.cout_ld, s));
+    ex.tap(h->stem_s.name, M, h->stem_s.cout_ld, hh, ww, h->stem_s.cout, SF_ONSET_PATH_STEM, false);
   } else {
     ex.conv(h->stem_s, p.in, H, W, M, hh, ww, nullptr, true);
   }
   ex.conv(h->stem_t, M, hh, ww, X, h2, w2, nullptr, true);
-  h->dbg.tap("stem", h->dt, X, h->stem_t.cout_ld, (int64_t)N * T * hh * ww, h->stem_t.cout, s);
+  ex.tap("stem", X, h->stem_t.cout_ld, hh, ww, h->stem_t.cout, 0, true);
   int bi = 0;
   for (const ResBlk &b : h->blocks) {
     int ho, wo, t1, t2;
@@ -298,7 +315,7 @@ int sf_onsetnet_forward(sf_onsetnet *h, const float *frames, int N, int T, int H
     }
     hh = ho;
     ww = wo;
-    if (bi % 2 == 1) h->dbg.tap(kStageName[bi / 2], h->dt, X, b.t2.cout_ld, (int64_t)N * T * hh * ww, b.t2.cout, s);
+    if (bi % 2 == 1) ex.tap(kStageName[bi / 2], X, b.t2.cout_ld, hh, ww, b.t2.cout, 0, true);
     ++bi;
   }
   // AdaptiveAvgPool3d((None,1,1)) -> (N*T, 512); Linear(512,128)+ReLU; Linear(128,1)
@@ -344,6 +361,17 @@ int sf_onsetnet_debug_enable(sf_onsetnet *h, float *buf, int64_t cap_floats) {
   h->dbg.cap = cap_floats;
   h->dbg.reset();
   return SF_OK;
+}
+int sf_onsetnet_debug_detail(sf_onsetnet *h, int enable, const int32_t *clips, int n_clips) {
+  if (!h || n_clips < 0 || (n_clips > 0 && !clips)) return SF_ERR_INVALID;
+  h->dbg.detail = enable != 0;
+  h->dbg.clips.assign(clips, clips + (enable ? n_clips : 0));
+  h->dbg.reset();
+  return SF_OK;
+}
+int sf_onsetnet_debug_path(const sf_onsetnet *h, int i) {
+  if (!h || i < 0 || i >= (int)h->dbg.entries.size()) return -1;
+  return h->dbg.entries[i].path;
 }
 int sf_onsetnet_debug_count(const sf_onsetnet *h) { return h ? (int)h->dbg.entries.size() : -1; }
 int sf_onsetnet_debug_info(const sf_onsetnet *h, int i, char *name_out, int name_cap, int64_t *offset, int64_t *rows, int32_t *cols) {
