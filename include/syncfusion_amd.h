@@ -469,6 +469,26 @@ int sf_op_video_to_cl(const float *x, int N, int C, int T, int H, int W, int ld,
 int sf_op_video_pool(const float *x, int64_t NT, int HW, int C, int ld, float *out, void *stream);
 int sf_op_video_pool_bwd(const float *dout, int64_t NT, int HW, int C, int ld, float *dx, void *stream);
 
+/* The optimizer stage of a training step: clip-by-global-norm and the AdamW update of EVERY listed tensor in three launches (two without
+ * clipping).  Replaces torch.nn.utils.clip_grad_norm_ (a per-tensor norm pass and a read-modify-write scaling pass over the gradients)
+ * followed by torch.optim.AdamW(fused=True).step() (exp/train_diffusion_gh.yaml:91-92 gradient_clip_val, main/module_diffusion.py:53-62 and
+ * main/module_onset.py AdamW), for fp32 contiguous tensors, amsgrad = False, maximize = False.
+ *   desc_dev   DEVICE memory, n_tensors records of 8 64-bit words, sorted by first_chunk: the addresses p, g, exp_avg, exp_avg_sq, step (an
+ *              fp32 scalar per tensor, as torch keeps it for its fused path), then the element count, then group | first_chunk << 32, then 0.
+ *              A tensor of n elements has ceil(n / SF_OPTIM_CHUNK) chunks; first_chunk is the running sum, total_chunks the total.
+ *   hyper_dev  DEVICE memory, (1 + n_groups) * 8 doubles: [0] max_norm; group g at 8 + 8 g: lr, beta1, beta2, eps, weight_decay.  Read by
+ *              the kernels at every call: a new learning rate is one small copy, also for a captured graph.
+ *   clip       1: total_norm = global L2 norm of the g, clip_coef = min(1, max_norm / (total_norm + 1e-6)); the update uses g * clip_coef,
+ *              g in memory is NOT scaled (clip_grad_norm_ scales .grad in place).  0: no norm pass, clip_coef = 1.
+ *   result_dev two floats: total_norm (written when clip = 1), clip_coef.
+ * Every step is incremented once per call; per element  p -= lr wd p;  m += (1 - beta1)(g' - m);  v = beta2 v + (1 - beta2) g'^2;
+ * p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps).  No atomics: identical input gives identical bits.  Non-finite
+ * gradients get no special treatment.  ws: 16-byte aligned, >= sf_optim_workspace_bytes(total_chunks) (-1 for total_chunks < 1). */
+#define SF_OPTIM_CHUNK 16384
+int64_t sf_optim_workspace_bytes(int total_chunks);
+int sf_optim_adamw_step(const void *desc_dev, int n_tensors, int total_chunks, const void *hyper_dev, int n_groups, int clip, float *result_dev,
+                        void *ws, int64_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,10 @@ SYMBOLS = {
     "sf_op_video_to_cl": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sf_op_video_pool": (_I, [_P, _L, _I, _I, _I, _P, _P]),
     "sf_op_video_pool_bwd": (_I, [_P, _L, _I, _I, _I, _P, _P]),
+    # the optimizer stage: clip-by-global-norm + AdamW over one device descriptor table (syncfusion_amd/optim.py)
+    "sf_optim_workspace_bytes": (_L, [_I]),
+    # (desc_dev, n_tensors, total_chunks, hyper_dev, n_groups, clip, result_dev, ws, ws_bytes, stream)
+    "sf_optim_adamw_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _L, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

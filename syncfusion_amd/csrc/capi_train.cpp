@@ -259,4 +259,31 @@ static int attention_bwd_lse_impl(int dtype, const float *q, const float *kv, co
   SF_API_END
 }
 
+static_assert(SF_OPTIM_CHUNK == OPTIM_CHUNK, "the header's chunk size is the kernels'");
+
+int64_t sf_optim_workspace_bytes(int total_chunks) {
+  if (total_chunks < 1) return -1;
+  return optim_ws_bytes(total_chunks);
+}
+
+int sf_optim_adamw_step(const void *desc_dev, int n_tensors, int total_chunks, const void *hyper_dev, int n_groups, int clip, float *result_dev,
+                        void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!desc_dev || !hyper_dev || !result_dev || !ws) fail(SF_ERR_INVALID, "sf_optim_adamw_step: null argument");
+  if (n_tensors <= 0) fail(SF_ERR_INVALID, "sf_optim_adamw_step: n_tensors must be positive (got %d)", n_tensors);
+  if (n_groups <= 0) fail(SF_ERR_INVALID, "sf_optim_adamw_step: n_groups must be positive (got %d)", n_groups);
+  if (total_chunks < n_tensors)
+    fail(SF_ERR_INVALID, "sf_optim_adamw_step: total_chunks %d < n_tensors %d: every tensor has at least one chunk", total_chunks, n_tensors);
+  if (clip != 0 && clip != 1) fail(SF_ERR_INVALID, "sf_optim_adamw_step: clip must be 0 or 1 (got %d)", clip);
+  if ((reinterpret_cast<uintptr_t>(desc_dev) & 7) || (reinterpret_cast<uintptr_t>(hyper_dev) & 7) || (reinterpret_cast<uintptr_t>(ws) & 15) ||
+      (reinterpret_cast<uintptr_t>(result_dev) & 3))
+    fail(SF_ERR_INVALID, "sf_optim_adamw_step: misaligned table, hyper-parameter array, result or workspace");
+  const int64_t need = optim_ws_bytes(total_chunks);
+  if (ws_bytes < need) fail(SF_ERR_WORKSPACE, "sf_optim_adamw_step: workspace too small: need %lld bytes, have %lld", (long long)need, (long long)ws_bytes);
+  SF_HIP(launch_optim_adamw_step(desc_dev, n_tensors, total_chunks, static_cast<const double *>(hyper_dev), n_groups, clip, result_dev, ws,
+                                 static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
 }  // extern "C"

@@ -502,6 +502,15 @@ hipError_t launch_bn_sync_bwd_apply(const float *x, const float *y /* ReLU mask 
 // backward of launch_spatial_mean: dx[(nt * HW + p) * ld + c] = dp[nt][c] / HW (zero for c >= C)
 hipError_t launch_pool_bwd(const float *dp, int64_t NT, int HW, int C, int ld, float *dx, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// Optimizer stage (optim.hip): clip-by-global-norm + AdamW over one device descriptor table (layout: optim.hip / sf_optim_adamw_step).
+// ws >= optim_ws_bytes(total_chunks), 16-byte aligned.  clip = 0: no norm pass, clip_coef = 1.
+// ---------------------------------------------------------------------------------------
+constexpr int OPTIM_CHUNK = 16384;   // elements per chunk = per workgroup
+int64_t optim_ws_bytes(int64_t total_chunks);
+hipError_t launch_optim_adamw_step(const void *desc_dev, int n_tensors, int total_chunks, const double *hyper_dev, int n_groups, int clip,
+                                   float *result_dev, void *ws, hipStream_t s);
+
 // BatchNorm (eval) -> per-channel scale / shift
 hipError_t launch_bn_fold(const float *gamma, const float *beta, const float *mean, const float *var, float eps, int C,
                           float *scale, float *shift, hipStream_t s);

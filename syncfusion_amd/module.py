@@ -77,13 +77,36 @@ class RandomEmbedder(nn.Module):
         return self._embed(feats.to(self.proj.device) + 1e-3)
 
 
+OPTIMIZERS = ("torch", "hip")
+
+
+def check_optimizer_choice(optimizer: str) -> str:
+    """The ``optimizer`` init-arg of both ``Model`` classes: ``"torch"`` (default: ``torch.optim.AdamW``, fused on the GPU) or ``"hip"``
+    (``syncfusion_amd.optim.AdamW``: the same update and the gradient clipping in the HIP library, when every parameter is on the GPU)."""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+    return optimizer
+
+
+def make_adamw(params, optimizer: str, **hyper) -> torch.optim.AdamW:
+    """``configure_optimizers`` of both ``Model`` classes: AdamW over ``params``; on the GPU torch's single-kernel (``fused``) step, or
+    with ``optimizer == "hip"`` the HIP class.  CPU parameters get the plain ``torch.optim.AdamW`` whatever ``optimizer`` says."""
+    on_gpu = bool(params) and all(p.is_cuda for p in params)
+    if optimizer == "hip" and on_gpu:
+        from .optim import AdamW
+
+        return AdamW(params, **hyper)
+    return torch.optim.AdamW(params, **hyper, **({"fused": True} if on_gpu else {}))
+
+
 VARIANTS_KEY = "syncfusion_amd.unet_variants"   # checkpoint entry next to `state_dict`: the three [RECALLED] facts of the U-Net
 
 
 class Model(_Base):
     def __init__(self, lr: float, lr_beta1: float, lr_beta2: float, lr_eps: float, lr_weight_decay: float,
-                 model: nn.Module, onsets_encoder: nn.Module, embedder: nn.Module, embedder_checkpoint: Optional[str]):
+                 model: nn.Module, onsets_encoder: nn.Module, embedder: nn.Module, embedder_checkpoint: Optional[str], optimizer: str = "torch"):
         super().__init__()
+        self.optimizer = check_optimizer_choice(optimizer)
         self.lr = lr
         self.lr_beta1 = lr_beta1
         self.lr_beta2 = lr_beta2
@@ -169,11 +192,11 @@ class Model(_Base):
 
     def configure_optimizers(self):
         """main/module_diffusion.py:53-61: AdamW over the U-Net and the onset encoder.  On the GPU the single-kernel (``fused``)
-        implementation of the same update is used: 4.2 instead of 8.7 ms for the 215 M parameters."""
+        implementation of the same update is used: 4.2 instead of 8.7 ms for the 215 M parameters.  ``optimizer="hip"`` (init-arg) returns
+        ``syncfusion_amd.optim.AdamW`` instead -- a ``torch.optim.AdamW`` whose step and gradient clipping are one call into the HIP library --
+        when every parameter is on the GPU."""
         params = list(self.model.parameters()) + list(self.onsets_encoder.parameters())
-        fused = bool(params) and all(p.is_cuda for p in params)
-        return torch.optim.AdamW(params, lr=self.lr, betas=(self.lr_beta1, self.lr_beta2), eps=self.lr_eps, weight_decay=self.lr_weight_decay,
-                                 **({"fused": True} if fused else {}))
+        return make_adamw(params, self.optimizer, lr=self.lr, betas=(self.lr_beta1, self.lr_beta2), eps=self.lr_eps, weight_decay=self.lr_weight_decay)
 
     @torch.no_grad()
     def clap_encode_audio(self, x: Tensor) -> Tensor:

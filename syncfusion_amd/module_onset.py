@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .module import _Base
+from .module import _Base, check_optimizer_choice, make_adamw
 from .onset_net import VideoOnsetNet
 
 Tensor = torch.Tensor
@@ -83,8 +83,10 @@ class BCLoss(nn.Module):
 class Model(_Base):
     """Drop-in for ``main.module_onset.Model`` (cfg/model/model-onset.yaml ``class_path``)."""
 
-    def __init__(self, lr: float, lr_beta1: float, lr_beta2: float, lr_eps: float, lr_weight_decay: float, onset_model: VideoOnsetNet):
+    def __init__(self, lr: float, lr_beta1: float, lr_beta2: float, lr_eps: float, lr_weight_decay: float, onset_model: VideoOnsetNet,
+                 optimizer: str = "torch"):
         super().__init__()
+        self.optimizer = check_optimizer_choice(optimizer)
         self.lr = lr
         self.lr_beta1 = lr_beta1
         self.lr_beta2 = lr_beta2
@@ -94,10 +96,9 @@ class Model(_Base):
         self.loss = BCLoss()
 
     def configure_optimizers(self) -> torch.optim.Optimizer:
-        params = list(self.model.parameters())
-        fused = bool(params) and all(p.is_cuda for p in params)   # the single-kernel multi-tensor AdamW on the GPU (module.py)
-        return torch.optim.AdamW(params, lr=self.lr, betas=(self.lr_beta1, self.lr_beta2), eps=self.lr_eps, weight_decay=self.lr_weight_decay,
-                                 **({"fused": True} if fused else {}))
+        # the single-kernel multi-tensor AdamW on the GPU; optimizer="hip": syncfusion_amd.optim.AdamW (module.py, make_adamw)
+        return make_adamw(list(self.model.parameters()), self.optimizer, lr=self.lr, betas=(self.lr_beta1, self.lr_beta2), eps=self.lr_eps,
+                          weight_decay=self.lr_weight_decay)
 
     def common_step(self, batch, batch_idx, mode: str = "train"):
         frames, labels = batch["frames"], batch["label"]

@@ -469,9 +469,28 @@ class GraphedTrainStep:
         for batch in loader:
             loss = gs.step(batch)                         # copy-in, refill randomness, replay
             optimizer.step()
+
+    With ``optimizer=`` a ``syncfusion_amd.optim.AdamW`` over these parameters, its step (gradient clipping included when its
+    ``max_grad_norm`` is set) is captured behind ``loss.backward()`` in the same graph: ``gs.step(batch)`` is then the WHOLE training step,
+    and new hyper-parameters (an LR scheduler's) reach the captured kernels through one small copy before the replay.  One warm-up
+    ``optimizer.step()`` runs before the capture so that the moments, step counters and the descriptor table exist; parameters, moments and
+    step counters are put back afterwards, so constructing the object does not train the model.  Refused when ``torch.distributed`` runs
+    more than one rank (the gradient all-reduce belongs between backward and update) and for any other optimizer class.
     """
 
-    def __init__(self, model, batch, warmup: int = 2):
+    def __init__(self, model, batch, warmup: int = 2, optimizer=None):
+        if optimizer is not None:
+            import torch.distributed as dist
+
+            from .optim import AdamW
+
+            if not isinstance(optimizer, AdamW):
+                raise TypeError(f"GraphedTrainStep: only syncfusion_amd.optim.AdamW can be captured with the step, got {type(optimizer).__name__} "
+                                "(step any other optimizer after gs.step(), with optimizer=None)")
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise RuntimeError("GraphedTrainStep: the optimizer cannot be captured with more than one rank: the gradient all-reduce belongs "
+                                   "between backward and the update (pass optimizer=None and step it after allreduce_gradients)")
+        self.optimizer = optimizer
         x, y, z = batch[0], batch[1], batch[2]
         self.model = model
         self.x, self.y, self.z = x.clone(), y.clone(), (x if z is x else z).clone()
@@ -487,6 +506,8 @@ class GraphedTrainStep:
                 for p in params:
                     p.grad = None
                 self._fwd_bwd()
+            if optimizer is not None:
+                self._warm_optimizer()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         for p in params:
@@ -494,6 +515,32 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph), training_step_scope():
             self.loss = self._fwd_bwd()
+            if optimizer is not None:
+                optimizer.step()
+        if optimizer is not None:
+            optimizer.sync_device_state()   # the table of the gradients the capture allocated: uploaded now, the captured kernels hold its address
+
+    def _warm_optimizer(self) -> None:
+        """One real ``optimizer.step()`` on the warm-up's gradients (creates the moments, the step counters, the table and the workspace
+        outside the capture), then everything it moved is put back."""
+        opt = self.optimizer
+        owned = [p for group in opt.param_groups for p in group["params"]]
+        saved_p = [p.detach().clone() for p in owned]
+        saved_state = {p: {k: (v.detach().clone() if isinstance(v, Tensor) else v) for k, v in opt.state[p].items()} for p in owned if p in opt.state}
+        opt.step()
+        with torch.no_grad():
+            for p, keep in zip(owned, saved_p):
+                p.copy_(keep)
+                st = opt.state.get(p)
+                if not st:
+                    continue
+                before = saved_state.get(p)
+                for k, v in st.items():
+                    if isinstance(v, Tensor):
+                        if before is not None and k in before:
+                            v.copy_(before[k])
+                        else:
+                            v.zero_()   # created by the warm-up step: a fresh moment / step counter is zero
 
     def _fwd_bwd(self) -> Tensor:
         m = self.model
@@ -515,6 +562,8 @@ class GraphedTrainStep:
         if resample:
             self.sig.uniform_()
             self.noise.normal_()
+        if self.optimizer is not None:
+            self.optimizer.sync_device_state()
         self.graph.replay()
         return self.loss
 
@@ -525,11 +574,15 @@ def fit_batches(model, optimizer, batches, *, accumulate_grad_batches: int = 2, 
     (exp/train_diffusion_gh.yaml:84-96: ``accumulate_grad_batches: 2``, ``gradient_clip_val: 0.5`` with Lightning's default
     clip-by-global-norm, fp32): the loss of every micro-batch is divided by the accumulation count, gradients are summed over
     ``accumulate_grad_batches`` micro-batches, averaged over the data-parallel ranks (``allreduce_gradients``), clipped to the
-    global L2 norm and applied.  A trailing incomplete accumulation window is applied as Lightning does at the end of an epoch.
+    global L2 norm and applied (a ``syncfusion_amd.optim.AdamW`` clips inside its own step and leaves ``.grad`` unscaled).  A trailing
+    incomplete accumulation window is applied as Lightning does at the end of an epoch.
     Returns the micro-batch losses.  ``on_step(step_index, mean_loss)`` is called after every optimizer step."""
     if accumulate_grad_batches < 1:
         raise ValueError("accumulate_grad_batches must be >= 1")
+    from .optim import AdamW as _HipAdamW
+
     params = [p for group in optimizer.param_groups for p in group["params"]]
+    hip_optimizer = isinstance(optimizer, _HipAdamW)
     losses: List[float] = []
     window: List[float] = []
     steps = 0
@@ -538,7 +591,10 @@ def fit_batches(model, optimizer, batches, *, accumulate_grad_batches: int = 2, 
         nonlocal steps
         allreduce_gradients(model)
         if gradient_clip_val is not None and gradient_clip_val > 0:
-            torch.nn.utils.clip_grad_norm_(params, gradient_clip_val)
+            if hip_optimizer:
+                optimizer.max_grad_norm = gradient_clip_val   # the clip is part of its step: no norm and scaling passes over the gradients
+            else:
+                torch.nn.utils.clip_grad_norm_(params, gradient_clip_val)
         optimizer.step()
         optimizer.zero_grad(set_to_none=True)
         steps += 1

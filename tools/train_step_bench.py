@@ -2,8 +2,12 @@
 """Time one training step of the reference's configuration (exp/train_diffusion_gh.yaml: fp32, batch 4 per device, clips of
 2^18 samples) on the HIP training path: Model.training_step -> loss.backward() -> AdamW.step().
 
-    python tools/train_step_bench.py [--batch 4] [--length 262144] [--steps 3] [--no-optimizer]
+    python tools/train_step_bench.py [--batch 4] [--length 262144] [--steps 3] [--no-optimizer] [--graph] [--optimizer {torch,hip}]
 Prints one JSON line: ms per step (forward / backward / optimizer), clips/s, peak HBM.
+
+--optimizer adds the reference's gradient clipping (gradient_clip_val 0.5) to the optimizer stage of both variants: `torch` =
+clip_grad_norm_ + torch.optim.AdamW(fused=True), `hip` = syncfusion_amd.optim.AdamW(max_grad_norm=0.5), which with --graph sits inside the
+captured graph (training.GraphedTrainStep(optimizer=...)): then only the whole step is timed.
 """
 from __future__ import annotations
 
@@ -15,6 +19,42 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+CLIP = 0.5   # exp/train_diffusion_gh.yaml:92
+
+
+def graphed_whole_step(args, torch, model, opt, batch) -> int:
+    """--graph --optimizer hip: forward, backward, clipping and AdamW in ONE graph; a step = refill the randomness, replay."""
+    from syncfusion_amd.training import GraphedTrainStep
+
+    gs = GraphedTrainStep(model, batch, optimizer=opt)
+    losses, t_s = [], 0.0
+    for it in range(args.warmup + args.steps):
+        gs.sig.uniform_()
+        gs.noise.normal_()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        gs.step(None, resample=False)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        losses.append(float(gs.loss))
+        if it >= args.warmup:
+            t_s += t1 - t0
+    total = t_s / args.steps
+    print(json.dumps({"workload": f"training step fp32 (graph replay incl. clip + AdamW on HIP), batch {args.batch}, L0 {args.length}", "fwd_bwd_ms": None,
+                      "optimizer_ms": None, "step_ms": 1e3 * total, "clips_per_s": args.batch / total, "optimizer": "hip",
+                      "peak_hbm_gb": torch.cuda.max_memory_allocated() / 1e9, "losses": losses}))
+    return 0
+
+
+def optimizer_stage(args, torch, opt, params):
+    """What runs behind backward: nothing / the plain step (no --optimizer: as before) / clipping at 0.5 + the step."""
+    if args.no_optimizer:
+        return
+    if args.optimizer == "torch":
+        torch.nn.utils.clip_grad_norm_(params, CLIP)
+    opt.step()
 
 
 def graphed(args, torch, model, opt, batch) -> int:
@@ -50,8 +90,7 @@ def graphed(args, torch, model, opt, batch) -> int:
         g.replay()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        if not args.no_optimizer:
-            opt.step()
+        optimizer_stage(args, torch, opt, params)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         losses.append(float(static_loss))
@@ -61,7 +100,7 @@ def graphed(args, torch, model, opt, batch) -> int:
     n = args.steps
     total = (t_g + t_o) / n
     print(json.dumps({"workload": f"training step fp32 (graph replay), batch {args.batch}, L0 {args.length}", "fwd_bwd_ms": 1e3 * t_g / n,
-                      "optimizer_ms": 1e3 * t_o / n, "step_ms": 1e3 * total, "clips_per_s": args.batch / total,
+                      "optimizer_ms": 1e3 * t_o / n, "step_ms": 1e3 * total, "clips_per_s": args.batch / total, "optimizer": args.optimizer,
                       "peak_hbm_gb": torch.cuda.max_memory_allocated() / 1e9, "losses": losses}))
     return 0
 
@@ -75,6 +114,9 @@ def main() -> int:
     ap.add_argument("--no-optimizer", action="store_true")
     ap.add_argument("--fused", action="store_true", help="torch.optim.AdamW(fused=True) with the reference's hyper-parameters")
     ap.add_argument("--graph", action="store_true", help="capture forward + backward in a torch CUDA graph (static batch buffers) and replay it")
+    ap.add_argument("--optimizer", choices=("torch", "hip"), default=None,
+                    help="optimizer stage WITH gradient clipping at 0.5: torch = clip_grad_norm_ + fused AdamW, hip = syncfusion_amd.optim.AdamW "
+                         "(inside the graph with --graph)")
     args = ap.parse_args()
     import torch
 
@@ -88,12 +130,19 @@ def main() -> int:
     if args.fused:
         opt = torch.optim.AdamW(list(model.model.parameters()) + list(model.onsets_encoder.parameters()), lr=model.lr, betas=(model.lr_beta1, model.lr_beta2),
                                 eps=model.lr_eps, weight_decay=model.lr_weight_decay, fused=True)
+    params = [p for group in opt.param_groups for p in group["params"]]
+    if args.optimizer == "hip":
+        from syncfusion_amd.optim import AdamW
+
+        opt = AdamW(params, lr=model.lr, betas=(model.lr_beta1, model.lr_beta2), eps=model.lr_eps, weight_decay=model.lr_weight_decay, max_grad_norm=CLIP)
     g = torch.Generator().manual_seed(1)
     x = torch.randn(args.batch, 1, args.length, generator=g).to(dev)
     y = (torch.rand(args.batch, 1, args.length, generator=g) < 0.0005).float().to(dev)
     batch = (x, y, x, None, None)
     t_f = t_b = t_o = 0.0
     losses = []
+    if args.graph and args.optimizer == "hip" and not args.no_optimizer:
+        return graphed_whole_step(args, torch, model, opt, batch)
     if args.graph:
         return graphed(args, torch, model, opt, batch)
     for it in range(args.warmup + args.steps):
@@ -106,8 +155,7 @@ def main() -> int:
         loss.backward()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-        if not args.no_optimizer:
-            opt.step()
+        optimizer_stage(args, torch, opt, params)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         losses.append(float(loss.detach()))
@@ -118,7 +166,7 @@ def main() -> int:
     n = args.steps
     total = (t_f + t_b + t_o) / n
     print(json.dumps({"workload": f"training step fp32, batch {args.batch}, L0 {args.length}", "forward_ms": 1e3 * t_f / n, "backward_ms": 1e3 * t_b / n,
-                      "optimizer_ms": 1e3 * t_o / n, "step_ms": 1e3 * total, "clips_per_s": args.batch / total,
+                      "optimizer_ms": 1e3 * t_o / n, "step_ms": 1e3 * total, "clips_per_s": args.batch / total, "optimizer": args.optimizer,
                       "peak_hbm_gb": torch.cuda.max_memory_allocated() / 1e9, "losses": losses}))
     return 0
 
