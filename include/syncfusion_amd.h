@@ -469,6 +469,25 @@ int sf_op_video_to_cl(const float *x, int N, int C, int T, int H, int W, int ld,
 int sf_op_video_pool(const float *x, int64_t NT, int HW, int C, int ld, float *out, void *stream);
 int sf_op_video_pool_bwd(const float *dout, int64_t NT, int HW, int C, int ld, float *dx, void *stream);
 
+/* The end of the onset training step (main/module_onset.py:268-354, BCLoss) from device memory to device memory: nothing is read back and
+ * nothing that changes per step is an argument, so the calls can sit inside a captured graph.  z: n fp32 logits, t: n fp32 labels (0 / 1).
+ *   sf_op_onset_bce_fwd   *loss = mean(pw t softplus(-z) + (1 - t) softplus(z)), pw = (n - sum t) / sum t computed on the device;
+ *                         stats[2] = (sum t, pw) for the backward call.  sum t == 0 gives pw = inf and a NaN loss, as the reference does.
+ *   sf_op_onset_bce_bwd   dz = *g / n * ((1 - t) sigmoid(z) - pw t (1 - sigmoid(z)));  g: the upstream scalar gradient, DEVICE memory.
+ *   sf_op_onset_metrics   z, t as (N, T) rows, N * T <= 2^24;  out[3] (fp64, device) = AP, Acc, OnsNumAcc of BCLoss.evaluate: scores are the
+ *                         fp32 sigmoid of z; the balanced subset is the first b = min(#(t == 1), #(t == 0)) positives and negatives in
+ *                         row-major order; AP = 1/b sum over the subset's positives i of TP(s >= s_i) / CNT(s >= s_i) (sklearn's step-wise
+ *                         average precision, tied scores as one threshold, in integer counts); Acc = share of the subset with
+ *                         (s > threshold) == t; OnsNumAcc = share of rows whose thresholded predictions, each run of L consecutive ones
+ *                         reduced to ceil(L / 2) (the reference's left-to-right suppression), count as many as the row's labels.
+ *                         b == 0 (one class only): AP = Acc = NaN, OnsNumAcc as usual.
+ * Every reduction runs in a fixed order without floating-point atomics: identical input gives identical bits.  ws: 8-byte aligned,
+ * >= sf_op_onset_loss_workspace_bytes(n) (one bound for the three calls at n = N * T; -1 for n < 1 or n >= 2^31). */
+int64_t sf_op_onset_loss_workspace_bytes(int64_t n);
+int sf_op_onset_bce_fwd(const float *z, const float *t, int64_t n, float *loss, float *stats, void *ws, int64_t ws_bytes, void *stream);
+int sf_op_onset_bce_bwd(const float *z, const float *t, const float *stats, const float *g, int64_t n, float *dz, void *stream);
+int sf_op_onset_metrics(const float *z, const float *t, int N, int T, float threshold, double *out, void *ws, int64_t ws_bytes, void *stream);
+
 /* The optimizer stage of a training step: clip-by-global-norm and the AdamW update of EVERY listed tensor in three launches (two without
  * clipping).  Replaces torch.nn.utils.clip_grad_norm_ (a per-tensor norm pass and a read-modify-write scaling pass over the gradients)
  * followed by torch.optim.AdamW(fused=True).step() (exp/train_diffusion_gh.yaml:91-92 gradient_clip_val, main/module_diffusion.py:53-62 and

@@ -14,11 +14,12 @@ from .generation import generate_batch, generate_dataset
 from .module import Model, RandomEmbedder
 from .module_onset import Model as OnsetModel
 from .onset_net import VideoOnsetNet
+from .onset_training import GraphedOnsetTrainStep
 from .onset_glue import cut_prefix_crop, onsets_to_track
 from .resample import resample
 from .training import allreduce_gradients
 
 __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule", "Encoder1d", "VideoOnsetNet", "Model", "OnsetModel",
-           "RandomEmbedder", "generate_batch", "generate_dataset", "instantiate", "instantiate_model_yaml", "onsets_to_track", "cut_prefix_crop", "resample",
+           "GraphedOnsetTrainStep",           "RandomEmbedder", "generate_batch", "generate_dataset", "instantiate", "instantiate_model_yaml", "onsets_to_track", "cut_prefix_crop", "resample",
            "allreduce_gradients", "frame_transforms", "instantiate_class", "instantiate_frames_transforms"]
 __version__ = "0.1.0"

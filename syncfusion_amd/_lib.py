@@ -161,6 +161,14 @@ SYMBOLS = {
     "sf_op_video_to_cl": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sf_op_video_pool": (_I, [_P, _L, _I, _I, _I, _P, _P]),
     "sf_op_video_pool_bwd": (_I, [_P, _L, _I, _I, _I, _P, _P]),
+    # the end of the onset training step: class-balanced BCE, its gradient and the step metrics (syncfusion_amd/onset_loss.py)
+    "sf_op_onset_loss_workspace_bytes": (_L, [_L]),
+    # (z, t, n, loss, stats, ws, ws_bytes, stream)
+    "sf_op_onset_bce_fwd": (_I, [_P, _P, _L, _P, _P, _P, _L, _P]),
+    # (z, t, stats, g, n, dz, stream)
+    "sf_op_onset_bce_bwd": (_I, [_P, _P, _P, _P, _L, _P, _P]),
+    # (z, t, N, T, threshold, out, ws, ws_bytes, stream)
+    "sf_op_onset_metrics": (_I, [_P, _P, _I, _I, _F, _P, _P, _L, _P]),
     # the optimizer stage: clip-by-global-norm + AdamW over one device descriptor table (syncfusion_amd/optim.py)
     "sf_optim_workspace_bytes": (_L, [_I]),
     # (desc_dev, n_tensors, total_chunks, hyper_dev, n_groups, clip, result_dev, ws, ws_bytes, stream)

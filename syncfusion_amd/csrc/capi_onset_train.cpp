@@ -1,5 +1,6 @@
 // VideoOnsetNet training: the op-level C-ABI entry points behind syncfusion_amd/onset_training.py (fp32; the reference trains the onset net in
-// fp32: cfg/trainer/trainer-onset*.yaml sets no precision).  Kernels: onset_train.hip, plus the implicit-GEMM forward (launch_conv_gemm, geom 1).
+// fp32: cfg/trainer/trainer-onset*.yaml sets no precision).  Kernels: onset_train.hip, plus the implicit-GEMM forward (launch_conv_gemm, geom 1);
+// onset_loss.hip for the loss and the step metrics behind syncfusion_amd/onset_loss.py.
 #include <algorithm>
 #include <exception>
 
@@ -232,6 +233,46 @@ int sf_op_video_pool_bwd(const float *dp, int64_t NT, int HW, int C, int ld, flo
   if (!dp || !dx) fail(SF_ERR_INVALID, "null argument");
   if (NT < 1 || HW < 1 || C < 1 || ld < C) fail(SF_ERR_INVALID, "bad shape");
   SF_HIP(launch_pool_bwd(dp, NT, HW, C, ld, dx, static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int64_t sf_op_onset_loss_workspace_bytes(int64_t n) {
+  if (n < 1 || n > INT32_MAX) return -1;
+  return onset_loss_ws_bytes(n);
+}
+
+int sf_op_onset_bce_fwd(const float *z, const float *t, int64_t n, float *loss, float *stats, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!z || !t || !loss || !stats || !ws) fail(SF_ERR_INVALID, "null argument");
+  if (n < 1 || n > INT32_MAX) fail(SF_ERR_INVALID, "1 <= n <= 2^31 - 1 required");
+  if ((uintptr_t)ws & 7u) fail(SF_ERR_INVALID, "misaligned workspace");
+  const int64_t need = onset_loss_ws_bytes(n);
+  if (ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  SF_HIP(launch_onset_bce_fwd(z, t, n, loss, stats, ws, static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_onset_bce_bwd(const float *z, const float *t, const float *stats, const float *g, int64_t n, float *dz, void *stream) {
+  SF_API_BEGIN
+  if (!z || !t || !stats || !g || !dz) fail(SF_ERR_INVALID, "null argument");
+  if (n < 1 || n > INT32_MAX) fail(SF_ERR_INVALID, "1 <= n <= 2^31 - 1 required");
+  SF_HIP(launch_onset_bce_bwd(z, t, stats, g, n, dz, static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_onset_metrics(const float *z, const float *t, int N, int T, float threshold, double *out, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!z || !t || !out || !ws) fail(SF_ERR_INVALID, "null argument");
+  if (N < 1 || T < 1) fail(SF_ERR_INVALID, "N >= 1 and T >= 1 required");
+  const int64_t n = (int64_t)N * T;
+  if (n > ONSET_METRICS_MAX) fail(SF_ERR_UNSUPPORTED, "step metrics take at most 2^24 logits (the AP count is quadratic in the balanced subset)");
+  if (((uintptr_t)ws | (uintptr_t)out) & 7u) fail(SF_ERR_INVALID, "misaligned workspace or output");
+  const int64_t need = onset_loss_ws_bytes(n);
+  if (ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  SF_HIP(launch_onset_metrics(z, t, N, T, threshold, out, ws, static_cast<hipStream_t>(stream)));
   return SF_OK;
   SF_API_END
 }

@@ -511,6 +511,20 @@ int64_t optim_ws_bytes(int64_t total_chunks);
 hipError_t launch_optim_adamw_step(const void *desc_dev, int n_tensors, int total_chunks, const double *hyper_dev, int n_groups, int clip,
                                    float *result_dev, void *ws, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// End of the onset training step (onset_loss.hip): class-balanced BCE-with-logits (main/module_onset.py:274-286), its gradient and the
+// step metrics [AP, Acc, OnsNumAcc] of BCLoss.evaluate (:288-354), all from device memory to device memory.  Fixed-order reductions, no
+// floating-point atomics.  ws >= onset_loss_ws_bytes(n), 8-byte aligned (one bound for the loss and the metrics of n = N * T elements).
+// ---------------------------------------------------------------------------------------
+constexpr int64_t ONSET_METRICS_MAX = (int64_t)1 << 24;   // the AP count is O(b^2) compares over the balanced subset
+int64_t onset_loss_ws_bytes(int64_t n);
+// loss (one float) and stats = (sum t, pos_weight) for the backward call
+hipError_t launch_onset_bce_fwd(const float *z, const float *t, int64_t n, float *loss, float *stats, void *ws, hipStream_t s);
+// dz = *g / n * ((1 - t) sigmoid(z) - pos_weight t (1 - sigmoid(z)));  g: the upstream scalar gradient, on the device
+hipError_t launch_onset_bce_bwd(const float *z, const float *t, const float *stats, const float *g, int64_t n, float *dz, hipStream_t s);
+// out[3] (fp64) = AP, Acc, OnsNumAcc of the (N, T) logits z and 0 / 1 labels t
+hipError_t launch_onset_metrics(const float *z, const float *t, int N, int T, float threshold, double *out, void *ws, hipStream_t s);
+
 // BatchNorm (eval) -> per-channel scale / shift
 hipError_t launch_bn_fold(const float *gamma, const float *beta, const float *mean, const float *var, float eps, int C,
                           float *scale, float *shift, hipStream_t s);

@@ -80,20 +80,37 @@ class BCLoss(nn.Module):
         return np.sum(np.sum(p, axis=-1) == np.sum(t, axis=-1)) / len(p)
 
 
+LOSSES = ("torch", "hip")
+
+
+def check_loss_choice(loss: str) -> str:
+    """The ``loss`` init-arg of ``Model``: ``"torch"`` (default: ``BCLoss``, ATen loss and host-side metrics, Python floats) or ``"hip"``
+    (``syncfusion_amd.onset_loss.DeviceBCLoss``: loss, gradient and metrics in the HIP library, metrics as device tensors, no host read)."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+    return loss
+
+
 class Model(_Base):
     """Drop-in for ``main.module_onset.Model`` (cfg/model/model-onset.yaml ``class_path``)."""
 
     def __init__(self, lr: float, lr_beta1: float, lr_beta2: float, lr_eps: float, lr_weight_decay: float, onset_model: VideoOnsetNet,
-                 optimizer: str = "torch"):
+                 optimizer: str = "torch", loss: str = "torch"):
         super().__init__()
         self.optimizer = check_optimizer_choice(optimizer)
+        self.loss_choice = check_loss_choice(loss)
         self.lr = lr
         self.lr_beta1 = lr_beta1
         self.lr_beta2 = lr_beta2
         self.lr_eps = lr_eps
         self.lr_weight_decay = lr_weight_decay
         self.model: VideoOnsetNet = onset_model
-        self.loss = BCLoss()
+        if self.loss_choice == "hip":
+            from .onset_loss import DeviceBCLoss
+
+            self.loss = DeviceBCLoss()
+        else:
+            self.loss = BCLoss()
 
     def configure_optimizers(self) -> torch.optim.Optimizer:
         # the single-kernel multi-tensor AdamW on the GPU; optimizer="hip": syncfusion_amd.optim.AdamW (module.py, make_adamw)
@@ -107,7 +124,7 @@ class Model(_Base):
         metrics = self.loss.evaluate(pred, labels)
         return loss, metrics
 
-    def log_metrics(self, metrics: Dict[str, float], mode: str = "val") -> None:
+    def log_metrics(self, metrics: Dict[str, object], mode: str = "val") -> None:
         for key, value in metrics.items():
             self.log(f"metrics/{mode}/{key}", value, on_step=False, on_epoch=True, prog_bar=True, logger=True, sync_dist=True)
 

@@ -17,7 +17,9 @@ whose channel counts are padded to the inference engine's row lengths (``ld``; z
   than one rank; everything else runs ``_BNTrain``, as ``torch.nn.SyncBatchNorm`` itself falls back to plain batch norm;
 * ``_Pool``     -- AdaptiveAvgPool3d((None, 1, 1)) (``sf_op_video_pool`` / ``sf_op_video_pool_bwd``).
 
-The fc head (0.01 % of the FLOPs), the pooled transpose and the loss run on ATen.  fp32 throughout (plain ``v_mfma_f32_32x32x2_f32``
+The fc head (0.01 % of the FLOPs) and the pooled transpose run on ATen; so does the loss, unless ``module_onset.Model(loss="hip")`` puts
+loss and step metrics on the device (syncfusion_amd/onset_loss.py) -- then ``GraphedOnsetTrainStep`` below replays the whole step from one
+HIP graph.  fp32 throughout (plain ``v_mfma_f32_32x32x2_f32``
 products): the reference trains the onset net in fp32.  No atomics: a second backward gives the same bits.
 """
 from __future__ import annotations
@@ -425,3 +427,100 @@ def onset_train_forward(net: nn.Module, x: Tensor, _force_sync: bool = False) ->
     h = feats.view(N, T, 512)
     h = F.relu(F.linear(h, net.fc[0].weight, net.fc[0].bias))
     return F.linear(h, net.fc[2].weight, net.fc[2].bias).squeeze(-1)
+
+
+# ---- the whole step from one graph ---------------------------------------------------------------------------------------------------------
+class GraphedOnsetTrainStep:
+    """``module_onset.Model.training_step`` + ``loss.backward()`` captured ONCE in a HIP graph and replayed per step (static batch shape): the
+    onset counterpart of ``training.GraphedTrainStep``, with the same rules.
+
+    The model must carry the device loss (``Model(..., loss="hip")``): ``BCLoss.evaluate`` reads the logits back on every step, which a
+    capture cannot hold.  ``batch`` is ``{"frames": (N, 3, T, H, W), "label": (N, T)}``; both are copied into static buffers.
+
+        gs = GraphedOnsetTrainStep(model, example_batch, optimizer=opt)   # build it BEFORE the first eager backward on these parameters
+        for batch in loader:
+            loss = gs.step(batch)                                         # copy-in, replay; gs.metrics = [AP, Acc, OnsNumAcc] of the step
+
+    ``loss`` and ``metrics`` are static device tensors that every replay overwrites (read them after the step, outside a timed loop).
+    Gradients land in the ``.grad`` tensors the capture allocated: do NOT ``zero_grad(set_to_none=True)`` afterwards.  With ``optimizer=`` a
+    ``syncfusion_amd.optim.AdamW`` its step (clipping included when ``max_grad_norm`` is set) is captured behind the backward pass, and
+    ``gs.step(batch)`` is the WHOLE training step; any other optimizer is stepped by the caller after ``gs.step()``.
+
+    Constructing the object does not train the model: the warm-up passes update the BatchNorm running statistics and ``num_batches_tracked``
+    (and one warm-up ``optimizer.step()`` moves parameters, moments and step counters); all of them are put back before the capture.  Every
+    ``step()`` advances the version counters of what the graph writes -- the running buffers, and the parameters when the optimizer is
+    captured -- so ``net.eval()`` rebuilds the inference engine as it does after an eager step.
+
+    Refused: more than one rank (the gradient all-reduce and the BatchNorm collectives run between the kernels) and a net with
+    ``nn.SyncBatchNorm`` modules while a process group is initialised."""
+
+    def __init__(self, model, batch, warmup: int = 2, optimizer=None):
+        from .onset_loss import DeviceBCLoss
+        from .optim import AdamW
+
+        if not isinstance(getattr(model, "loss", None), DeviceBCLoss):
+            raise ValueError('GraphedOnsetTrainStep: the model must be built with loss="hip" (syncfusion_amd.onset_loss.DeviceBCLoss): '
+                             f"{type(getattr(model, 'loss', None)).__name__}.evaluate reads the logits back on the host, which a capture cannot hold")
+        if optimizer is not None and not isinstance(optimizer, AdamW):
+            raise TypeError(f"GraphedOnsetTrainStep: only syncfusion_amd.optim.AdamW can be captured with the step, got {type(optimizer).__name__} "
+                            "(step any other optimizer after gs.step(), with optimizer=None)")
+        if dist.is_available() and dist.is_initialized():
+            if dist.get_world_size() > 1:
+                raise RuntimeError("GraphedOnsetTrainStep: capture is supported on the single-rank path only (the gradient all-reduce and the "
+                                   "collectives of a synchronised BatchNorm run between the kernels)")
+            if any(isinstance(m, nn.SyncBatchNorm) for m in model.modules()):
+                raise RuntimeError("GraphedOnsetTrainStep: the net holds nn.SyncBatchNorm modules and a process group is initialised: a step with "
+                                   "synchronised BatchNorm cannot be captured into a HIP graph")
+        if not model.model.training:
+            raise RuntimeError("GraphedOnsetTrainStep: the onset net is in eval mode; call .train() first")
+        self.model, self.optimizer = model, optimizer
+        self.batch = {"frames": batch["frames"].clone(), "label": batch["label"].clone()}
+        params = [p for p in model.parameters() if p.requires_grad]
+        buffers = [b for b in model.buffers() if b is not None]
+        keep = [b.detach().clone() for b in buffers]
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):     # warm-up on a side stream: allocator pools, lazy kernel loads, the growing workspace, .grad allocation
+            for _ in range(max(1, warmup)):
+                for p in params:
+                    p.grad = None
+                self._fwd_bwd()
+            if optimizer is not None:
+                self._warm_optimizer()
+            with torch.no_grad():
+                for b, k in zip(buffers, keep):
+                    b.copy_(k)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        for p in params:
+            p.grad = None
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.loss = self._fwd_bwd()
+            if optimizer is not None:
+                optimizer.step()
+        self.metrics = model.loss.last_metrics
+        if optimizer is not None:
+            optimizer.sync_device_state()   # the table of the gradients the capture allocated: uploaded now, the captured kernels hold its address
+        self._written = buffers + ([p for group in optimizer.param_groups for p in group["params"]] if optimizer is not None else [])
+
+    def _warm_optimizer(self) -> None:
+        from .training import GraphedTrainStep
+
+        GraphedTrainStep._warm_optimizer(self)   # one real step on the warm-up's gradients, then parameters, moments and counters put back
+
+    def _fwd_bwd(self) -> Tensor:
+        loss = self.model.training_step(self.batch, 0)
+        loss.backward()
+        return loss
+
+    def step(self, batch=None) -> Tensor:
+        """Copy ``batch`` (same shapes as the example) into the static buffers and replay.  Returns the static loss tensor."""
+        if batch is not None:
+            self.batch["frames"].copy_(batch["frames"])
+            self.batch["label"].copy_(batch["label"])
+        if self.optimizer is not None:
+            self.optimizer.sync_device_state()
+        self.graph.replay()
+        _bump(*self._written)
+        return self.loss
