@@ -140,6 +140,12 @@ class PackPlan:
         self.total_tiles, self.n_packed, self.state, self.misses = tiles, len(packed), "ready", 0
 
 
+def conv1d_workspace_bytes(B: int, C: int, N: int, taps: int, groups: int) -> int:
+    """Scratch bytes handed to sf_op_conv1d_cl / sf_op_conv1d_train_fwd, which have no size query (weight images, GroupNorm chunk
+    statistics, slack)."""
+    return max(256, 12 * N * C * taps + 8 * B * 64 * groups + (1 << 16))
+
+
 _TLS = threading.local()   # .plan: the PackPlan of the forward pass running on THIS thread (None outside ``with plan:``)
 
 
@@ -182,7 +188,7 @@ class _ConvBlockFn(torch.autograd.Function):
             g = _lib.f32c(gamma) if groups > 0 else None
             be = _lib.f32c(beta) if groups > 0 else None
             out = torch.empty(B, L, N, dtype=torch.float32, device=x.device)
-            ws = torch.empty(max(256, 12 * N * Cc * taps + 8 * B * 64 * groups + (1 << 16)), dtype=torch.uint8, device=x.device)
+            ws = torch.empty(conv1d_workspace_bytes(B, Cc, N, taps, groups), dtype=torch.uint8, device=x.device)
             # residual: added in the convolution's epilogue (one pass less over the tensor than a separate add); its gradient is dy itself
             res_cl, res_late = None, None
             if residual is not None:
