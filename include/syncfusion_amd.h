@@ -330,6 +330,10 @@ int sf_op_conv1d_bwd_cl_p(int dtype, const float *x, const float *act, const flo
  * total_tiles is their sum.  sf_op_conv1d_train_fwd_pk = sf_op_conv1d_train_fwd reading fw / fwx instead of packing; the backward pass
  * takes the weight's [dg | dgx] region (dgx at dg + 4 * C * taps * N bytes) as the dgrad_pack of sf_op_conv1d_bwd_cl_p. */
 int sf_op_conv1d_train_images(int dtype, const float *w, int B, int L, int C, int N, int taps, int pad, int groups);
+/* Which kernel sf_op_conv1d_cl(dtype, ...) launches for this geometry: writes its label (the profiling label of the GEMM variant, or
+ * "conv_direct" for the thin path, C % 32 != 0) into label[label_bytes].  Query only: nothing is launched and no device is needed.  The
+ * label comes from the same finished launch arguments as the real call's (tests pin a case to the kernel family it is meant for). */
+int sf_op_conv1d_variant(int dtype, int B, int L, int C, int N, int taps, int stride, int pad, int upsample, int groups, char *label, int label_bytes);
 int sf_train_pack_many(const void *desc_dev, int n_items, int total_tiles, void *stream);
 int sf_op_conv1d_train_fwd_pk(int dtype, const float *x, const float *w, const float *fw, const void *fwx, const float *bias, const float *gamma,
                               const float *beta, int groups, float eps, const float *residual, int B, int L, int C, int N, int taps, int pad, float *out,

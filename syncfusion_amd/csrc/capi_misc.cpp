@@ -196,17 +196,22 @@ int sf_resampler_forward(sf_resampler *h, const float *x, int R, int L, float *o
 // (dgp: the training forward also writes the data-gradient images of the weight, [C][taps][N] fp32 then its split bf16 image, for
 // sf_op_conv1d_bwd_cl_p -- one pack launch per weight and step instead of one per GEMM)
 // (prepacked: the images come from sf_train_pack_many -- pk_fw / pk_fwx as sf_op_conv1d_train_images says; nothing is packed here.
-//  images_out: query only -- which images would the training forward (with / without a data gradient) read?  Nothing is launched.)
+//  images_out: query only -- which images would the training forward (with / without a data gradient) read?  Nothing is launched.
+//  label_out: query only -- the label of the launch these arguments end in (sf_op_conv1d_variant).  The ConvGemmArgs are finished by the
+//  same statements as for a real call: every image is a probe pointer where the real call allocates it, and nothing is launched.)
 enum { IMG_FW = 1, IMG_FWX = 2, IMG_DG = 4, IMG_DGX = 8, IMG_UNPLANNABLE = 16 };
 static int conv1d_cl_impl(int dtype, const void *x, const float *w, const float *bias, const float *gamma, const float *beta, int groups,
                           float eps, const void *residual, int B, int L, int C, int N, int taps, int stride, int pad, int upsample,
                           void *out, void *ws, int64_t ws_bytes, void *stream, void *dgp, bool prepacked = false, const float *pk_fw = nullptr,
-                          const void *pk_fwx = nullptr, int *images_out = nullptr) {
+                          const void *pk_fwx = nullptr, int *images_out = nullptr, const char **label_out = nullptr) {
   SF_API_BEGIN
-  if (!images_out && (!x || !w || !out || !ws)) fail(SF_ERR_INVALID, "null argument");
+  const bool query = images_out || label_out;
+  if (!query && (!x || !w || !out || !ws)) fail(SF_ERR_INVALID, "null argument");
   if (upsample < 1 || (upsample & (upsample - 1))) fail(SF_ERR_UNSUPPORTED, "upsample must be a power of two");
   hipStream_t s = static_cast<hipStream_t>(stream);
   Workspace wk(ws, ws_bytes);
+  // a weight image: workspace for a real call, a probe pointer for the label query (the decisions depend on which images exist, not on their contents)
+  auto image = [&](int64_t bytes) -> void * { return label_out ? reinterpret_cast<void *>(16) : wk.alloc(bytes); };
   const bool x3 = dtype == SF_F32X;   // fp32 tensors, products from split fp16 operands (needs N * K * 4 more bytes of workspace)
   if (x3) dtype = F32;
   const bool direct = (C % 32) != 0;
@@ -236,8 +241,8 @@ static int conv1d_cl_impl(int dtype, const void *x, const float *w, const float 
   a.solo = 1;   // op-level entry (the training step's single stream)
   if (groups > 0) {
     GnPlan gp = gn_plan(B, L, C);
-    float *slab = images_out ? nullptr : wk.alloc_n<float>((int64_t)B * gp.nch * groups * 2);
-    if (!images_out) SF_HIP(launch_gn_stats(dtype, x, C, B, L, C, groups, gp.nch, gp.chunk_rows, slab, s));
+    float *slab = query ? nullptr : wk.alloc_n<float>((int64_t)B * gp.nch * groups * 2);
+    if (!query) SF_HIP(launch_gn_stats(dtype, x, C, B, L, C, groups, gp.nch, gp.chunk_rows, slab, s));
     a.pro = 1;
     a.G = groups;
     a.nch = gp.nch;
@@ -287,31 +292,36 @@ static int conv1d_cl_impl(int dtype, const void *x, const float *w, const float 
     if (fw) wp = fw;
     else if (need_fw) wp = nullptr;   // nobody reads it
   } else if (need_fw) {
-    void *packed = wk.alloc((int64_t)N * K * dsize(wdt));
+    void *packed = image((int64_t)N * K * dsize(wdt));
     if (wx_ok) {   // fp32 matrix and its split image in one pass
-      wx_done = wk.alloc((int64_t)N * K * 4);
-      SF_HIP(launch_pack_conv_x(w, N, C, taps, static_cast<float *>(packed), wx_done, X3_F16, s));
-    } else {
+      wx_done = image((int64_t)N * K * 4);
+      if (!label_out) SF_HIP(launch_pack_conv_x(w, N, C, taps, static_cast<float *>(packed), wx_done, X3_F16, s));
+    } else if (!label_out) {
       SF_HIP(launch_pack_conv(wdt, w, N, C, 0, C, taps, C, nullptr, packed, K, 0, s));
     }
     wp = packed;
   }
   if (!direct && dtype != F32 && (K % 64) == 0 && K <= 2048 && (N % 32) == 0 && (C % 16) == 0) {   // as the engine packs it (conv_gemm_rs.hip)
-    void *wfr = wk.alloc((int64_t)N * K * dsize(wdt));
-    SF_HIP(launch_pack_wfr(dtype, wp, N, K, wfr, s));
+    void *wfr = image((int64_t)N * K * dsize(wdt));
+    if (!label_out) SF_HIP(launch_pack_wfr(dtype, wp, N, K, wfr, s));
     a.wfr = wfr;
   }
   if (wx_done) a.wx = wx_done;
   else if (wx_ok) {
-    void *wx = wk.alloc((int64_t)N * K * 4);
-    SF_HIP(launch_pack_wx(static_cast<const float *>(wp), N, K, wx, s));
+    void *wx = image((int64_t)N * K * 4);
+    if (!label_out) SF_HIP(launch_pack_wx(static_cast<const float *>(wp), N, K, wx, s));
     a.wx = wx;
   }
   a.w = wp;
   if (want_rs) {
-    void *wfrx = wk.alloc((int64_t)N * K * 4);
-    SF_HIP(launch_pack_wfrx(static_cast<const float *>(wp), N, K, wfrx, s));
+    void *wfrx = image((int64_t)N * K * 4);
+    if (!label_out) SF_HIP(launch_pack_wfrx(static_cast<const float *>(wp), N, K, wfrx, s));
     a.wfrx = wfrx;
+  }
+  if (label_out) {   // the ConvGemmArgs are finished: name the launch below instead of making it
+    if (!direct && !conv_gemm_supported(dtype, a)) fail(SF_ERR_UNSUPPORTED, "no GEMM kernel takes this shape");
+    *label_out = direct ? "conv_direct" : conv_gemm_variant_name(dtype, a);
+    return SF_OK;
   }
   if (direct) SF_HIP(launch_conv_direct(dtype, dtype, a, s));
   else SF_HIP(launch_conv_gemm(dtype, a, s));
@@ -353,6 +363,25 @@ int sf_op_conv1d_train_images(int dtype, const float *w, int B, int L, int C, in
   const int rc = conv1d_cl_impl(dtype, nullptr, w, nullptr, nullptr, nullptr, groups, 0.f, nullptr, B, L, C, N, taps, 1, pad, 1, nullptr, nullptr, 0, nullptr, nullptr,
                                 false, nullptr, nullptr, &mask);
   return rc == SF_OK ? mask : -1;
+}
+
+int sf_op_conv1d_variant(int dtype, int B, int L, int C, int N, int taps, int stride, int pad, int upsample, int groups, char *label, int label_bytes) {
+  if (!label || label_bytes < 1) {
+    set_error("sf_op_conv1d_variant: no room for the label");
+    return SF_ERR_INVALID;
+  }
+  label[0] = 0;
+  if (B < 1 || L < 1 || C < 1 || N < 1 || taps < 1 || stride < 1 || pad < 0 || groups < 0 || upsample < 1 || (int64_t)L * upsample + 2 * pad < taps) {
+    set_error("sf_op_conv1d_variant: bad geometry");
+    return SF_ERR_INVALID;
+  }
+  const char *name = nullptr;
+  const float *probe = reinterpret_cast<const float *>(16);   // an aligned weight, as a tensor's storage is
+  const int rc = conv1d_cl_impl(dtype, nullptr, probe, nullptr, nullptr, nullptr, groups, 0.f, nullptr, B, L, C, N, taps, stride, pad, upsample, nullptr, nullptr, 0,
+                                nullptr, nullptr, false, nullptr, nullptr, nullptr, &name);
+  if (rc != SF_OK) return rc;
+  snprintf(label, (size_t)label_bytes, "%s", name);
+  return SF_OK;
 }
 
 int sf_train_pack_many(const void *desc_dev, int n_items, int total_tiles, void *stream) {
