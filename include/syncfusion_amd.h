@@ -512,6 +512,46 @@ int64_t sf_optim_workspace_bytes(int total_chunks);
 int sf_optim_adamw_step(const void *desc_dev, int n_tensors, int total_chunks, const void *hyper_dev, int n_groups, int clip, float *result_dev,
                         void *ws, int64_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Audio front end of the onset-sync evaluation (syncfusion_amd/audio_features.py, evaluation.py)
+ *   replaces: librosa.onset.onset_detect(y=wav, sr=22050, units='samples', delta=0.3) at script/evaluate_onset.py:30 (log-mel spectrogram,
+ *   spectral flux, peak picking), the waveform confidences of eval_osnets (script/evaluate_onset.py:52-54), and the
+ *   torchaudio.transforms.MelSpectrogram + power_to_db pair of SampleLogger (main/module_diffusion.py:120-152).
+ * All tensors fp32 (counts and positions int32), contiguous, on the device; T = 1 + L / hop frames (center = True).
+ *
+ * sf_audio_features_create   HOST-only: checks the configuration and builds the periodic Hann window and the twiddle table in fp64
+ *     (rounded once to fp32).  n_fft: a power of two in [256, 4096]; hop, n_mels >= 1; pad_mode 0 = constant (zeros), 1 = reflect (no
+ *     edge repeat, as torch.stft).  The mel filterbank comes from the host in compact form: filter m touches bins first_bin[m] ..
+ *     first_bin[m] + bin_count[m] - 1 (bin_count >= 1, inside 0 .. n_fft / 2) with the weights packed one filter after the other
+ *     (n_weights = sum of bin_count).  The tables are copied to the device once, at the first forward call on the handle.
+ * sf_audio_features_workspace_bytes   one bound for both calls (monotone in B and L; -1 for a null handle, B < 1 or L < 1).
+ * sf_logmel_forward   wav (B, L) -> mel_power (B, n_mels, T) and / or db (B, n_mels, T), either may be NULL (not both):
+ *     frame t = samples [t hop - n_fft / 2, t hop + n_fft / 2) of the padded clip, times the window, n_fft-point real DFT, |X_k|^2,
+ *     filterbank;  db = max(10 log10(max(amin, P)), max over the clip's plane - top_db)  (power_to_db with ref = 1).
+ * sf_onset_detect     the whole detector in one call: envelope (B, T), count (B), positions / confidence / strength (B, capacity).
+ *     d[t] = mean_m max(0, db[m, t] - db[m, t - lag]) for t >= lag; envelope = lag + n_fft / (2 hop) zero frames followed by those
+ *     values, cut to T frames (d[t] lands at frame t + n_fft / (2 hop)).  An all-zero envelope has no onsets.  Otherwise
+ *     x = (e - min e) / (max(e - min e) + FLT_MIN) and frame n is an onset when x[n] is the maximum of x[max(0, n - pre_max) :
+ *     min(T, n + post_max)], x[n] >= mean(x[max(0, n - pre_avg) : min(T, n + post_avg)]) + delta, and n - previous onset > wait.
+ *     positions = n hop (samples, ascending; unused slots -1); confidence = max(w[max(0, o - conf_interval) : min(L, o + conf_interval)])
+ *     and strength = w[o] (0 where o == L) with w = (|wav| - min |wav|) / (max |wav| - min |wav|); unused slots 0.
+ *     count[b] = -1 when clip b has more than `capacity` onsets (nothing is truncated silently; capacity = T can never overflow).
+ * Refused before any HIP call: null pointers, B < 1, L < 1 (SF_ERR_INVALID); reflect padding with L <= n_fft / 2, B > 65535 or
+ * B n_mels T >= 2^31 (SF_ERR_SHAPE); a workspace below the query (SF_ERR_WORKSPACE); lag, post_max, post_avg, conf_interval,
+ * capacity < 1, pre_max, pre_avg, wait < 0, amin <= 0, top_db < 0 (SF_ERR_INVALID).  A clip's results do not depend on the rest of
+ * the batch (fixed-order reductions, no atomics). */
+typedef struct sf_audio_features sf_audio_features;
+enum { SF_PAD_CONSTANT = 0, SF_PAD_REFLECT = 1 };
+int sf_audio_features_create(int n_fft, int hop, int n_mels, int pad_mode, const int32_t *first_bin /*host*/, const int32_t *bin_count /*host*/,
+                             const float *weights /*host*/, int64_t n_weights, sf_audio_features **out);
+void sf_audio_features_destroy(sf_audio_features *h);
+int64_t sf_audio_features_workspace_bytes(const sf_audio_features *h, int B, int L);
+int sf_logmel_forward(sf_audio_features *h, const float *wav, int B, int L, float amin, float top_db, float *mel_power, float *db, void *ws,
+                      int64_t ws_bytes, void *stream);
+int sf_onset_detect(sf_audio_features *h, const float *wav, int B, int L, float amin, float top_db, int lag, int pre_max, int post_max,
+                    int pre_avg, int post_avg, int wait, float delta, int conf_interval, int capacity, float *envelope, int32_t *count,
+                    int32_t *positions, float *confidence, float *strength, void *ws, int64_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

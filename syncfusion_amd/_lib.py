@@ -175,6 +175,16 @@ SYMBOLS = {
     "sf_optim_workspace_bytes": (_L, [_I]),
     # (desc_dev, n_tensors, total_chunks, hyper_dev, n_groups, clip, result_dev, ws, ws_bytes, stream)
     "sf_optim_adamw_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _L, _P]),
+    # the audio front end of the onset-sync evaluation (syncfusion_amd/audio_features.py)
+    # (n_fft, hop, n_mels, pad_mode, first_bin_host, bin_count_host, weights_host, n_weights, out)
+    "sf_audio_features_create": (_I, [_I, _I, _I, _I, _P, _P, _P, _L, C.POINTER(_P)]),
+    "sf_audio_features_destroy": (None, [_P]),
+    "sf_audio_features_workspace_bytes": (_L, [_P, _I, _I]),
+    # (h, wav, B, L, amin, top_db, mel_power, db, ws, ws_bytes, stream)
+    "sf_logmel_forward": (_I, [_P, _P, _I, _I, _F, _F, _P, _P, _P, _L, _P]),
+    # (h, wav, B, L, amin, top_db, lag, pre_max, post_max, pre_avg, post_avg, wait, delta, conf_interval, capacity, envelope, count, positions,
+    #  confidence, strength, ws, ws_bytes, stream)
+    "sf_onset_detect": (_I, [_P, _P, _I, _I, _F, _F, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
 }
 
 _lib: Optional[C.CDLL] = None
