@@ -334,6 +334,14 @@ int sf_op_conv1d_train_images(int dtype, const float *w, int B, int L, int C, in
  * "conv_direct" for the thin path, C % 32 != 0) into label[label_bytes].  Query only: nothing is launched and no device is needed.  The
  * label comes from the same finished launch arguments as the real call's (tests pin a case to the kernel family it is meant for). */
 int sf_op_conv1d_variant(int dtype, int B, int L, int C, int N, int taps, int stride, int pad, int upsample, int groups, char *label, int label_bytes);
+/* The launches sf_op_conv1d_bwd_cl_x(dtype, ..., groups = 0) makes for this geometry (dtype SF_F32 or SF_F32X), as one string
+ *   "dgrad <kernel> | <wgrad kernel> S=<row splits> <reducer> | db <column-sum kernel> Sb=<bias slices>"
+ * <kernel>: the data-gradient GEMM's variant label ("<x3" in it: the split bf16 weight image is read), "conv_direct" (N % 32 != 0), or
+ * "refused" (N % 32 != 0 with C > 32: the entry computes no dx for it); <wgrad kernel>: wgrad_thin<1,TQ>, or wgrad_lds<TW>/tap|rows,
+ * wgrad_x3<TW>/tap|rows (single-tap or whole-rows staging); <reducer>: direct (S = 1: no reduce pass), vec or scalar; <column-sum
+ * kernel>: vec4, vec1 or generic.  Query only: nothing is launched and no device is needed; it calls the plan functions the launchers
+ * switch on. */
+int sf_op_conv1d_bwd_variant(int dtype, int B, int L, int C, int N, int taps, int pad, char *label, int label_bytes);
 int sf_train_pack_many(const void *desc_dev, int n_items, int total_tiles, void *stream);
 int sf_op_conv1d_train_fwd_pk(int dtype, const float *x, const float *w, const float *fw, const void *fwx, const float *bias, const float *gamma,
                               const float *beta, int groups, float eps, const float *residual, int B, int L, int C, int N, int taps, int pad, float *out,

@@ -116,6 +116,7 @@ SYMBOLS = {
     "sf_op_conv1d_train_images": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I]),
     # (dtype, B, L, C, N, taps, stride, pad, upsample, groups, label, label_bytes)
     "sf_op_conv1d_variant": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
+    "sf_op_conv1d_bwd_variant": (_I, [_I, _I, _I, _I, _I, _I, _I, C.c_char_p, _I]),
     "sf_train_pack_many": (_I, [_P, _I, _I, _P]),
     # (dtype, x, w, fw, fwx, bias, gamma, beta, groups, eps, residual, B, L, C, N, taps, pad, out, ws, ws_bytes, stream)
     "sf_op_conv1d_train_fwd_pk": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _I, _I, _I, _I, _I, _I, _P, _P, _L, _P]),

@@ -26,6 +26,26 @@ struct BwdPlan {
   int S = 1, Sb = 1, ldn = 0;
 };
 
+int bias_slices(int64_t rows, int N) { return (int)std::min<int64_t>(256, std::max<int64_t>(1, rows * N / 16384)); }   // >= 16 K elements per slice
+
+// The data-gradient launch of conv1d_bwd_impl without its weight images: which kernel family takes it (conv_direct for N % 32 != 0, which
+// the entry refuses for C > 32), whether the split bf16 image is packed and handed over, and the GEMM arguments.  The entry adds the images it
+// packed, sf_op_conv1d_bwd_variant probe pointers in the same places.
+struct DgradPlan {
+  bool direct = false, refused = false, split = false;
+  ConvGemmArgs a;
+};
+DgradPlan dgrad_plan(bool x3, const float *dy, int B, int L, int C, int N, int taps, int pad, float *out) {
+  DgradPlan d;
+  d.direct = (N % 32) != 0;
+  d.split = conv1d_dgrad_split_ok(x3, N, taps);
+  d.a = conv1d_dgrad_args(dy, B, L, C, N, taps, pad, out);
+  d.refused = d.direct && (C > 32 || !conv_direct_supported(d.a));
+  if (!d.split) d.a.wx_mode = X3_F16;   // (unused without a split image; the struct's default)
+  return d;
+}
+bool bwd_geometry_ok(int taps, int pad) { return !(taps < 1 || pad < 0 || pad >= taps || 2 * pad != taps - 1); }
+
 BwdPlan plan(Workspace &ws, int B, int L, int C, int N, int taps, int groups) {
   BwdPlan p;
   const int64_t rows = (int64_t)B * L;
@@ -36,7 +56,7 @@ BwdPlan plan(Workspace &ws, int B, int L, int C, int N, int taps, int groups) {
   p.wdx = ws.alloc((int64_t)C * taps * p.ldn * 4);
   p.S = conv_wgrad_splits(rows, C, N, taps);
   p.wpart = ws.alloc_n<float>((int64_t)p.S * N * taps * C);
-  p.Sb = (int)std::min<int64_t>(256, std::max<int64_t>(1, rows * N / 16384));   // >= 16 K elements per slice
+  p.Sb = bias_slices(rows, N);
   p.bpart = ws.alloc_n<float>((int64_t)p.Sb * N);
   if (groups > 0) p.gpart = ws.alloc_n<float>(gn_silu_bwd_ws_floats(B, L, C, groups));
   return p;
@@ -68,7 +88,7 @@ static int conv1d_bwd_impl(int dtype, const float *x, const float *act_saved, co
   if (!dx && !dw && !db && !dgb) fail(SF_ERR_INVALID, "nothing to compute: dx, dw, db and dgb are all null");
   if (groups > 0 && (!gamma || !beta || !dgb || !dx)) fail(SF_ERR_INVALID, "GroupNorm backward needs gamma, beta, dgb and dx");
   if (dx_add && groups <= 0) fail(SF_ERR_UNSUPPORTED, "dx_add: GroupNorm convolutions only");
-  if (taps < 1 || pad < 0 || pad >= taps || 2 * pad != taps - 1) fail(SF_ERR_UNSUPPORTED, "stride-1 'same' convolutions only (2 * pad == taps - 1)");
+  if (!bwd_geometry_ok(taps, pad)) fail(SF_ERR_UNSUPPORTED, "stride-1 'same' convolutions only (2 * pad == taps - 1)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   Workspace wk(ws, ws_bytes);
   BwdPlan p = plan(wk, B, L, C, N, taps, groups);
@@ -84,11 +104,10 @@ static int conv1d_bwd_impl(int dtype, const float *x, const float *act_saved, co
   // (dx == NULL: the input needs no gradient -- the first convolution on the raw waveform, a frozen trunk -- and without a GroupNorm
   // in front nothing else depends on da: the whole data gradient is skipped; likewise dw == NULL skips the weight gradient)
   if (dx || groups > 0) {
-    const bool direct = (N % 32) != 0;
-    if (direct && C > 32) fail(SF_ERR_UNSUPPORTED, "dgrad of a thin convolution (N %% 32 != 0) needs C <= 32");
-    const bool wx_dg = conv1d_dgrad_split_ok(x3, N, taps);
-    ConvGemmArgs a = conv1d_dgrad_args(dy, B, L, C, N, taps, pad, groups > 0 ? p.da : dx);
-    if (!wx_dg) a.wx_mode = X3_F16;   // (unused without a split image; the struct's default)
+    DgradPlan dg = dgrad_plan(x3, dy, B, L, C, N, taps, pad, groups > 0 ? p.da : dx);
+    if (dg.refused) fail(SF_ERR_UNSUPPORTED, "dgrad of a thin convolution (N %% 32 != 0) needs C <= 32 and its weight matrix within conv_direct's 64 KiB of LDS");
+    const bool direct = dg.direct, wx_dg = dg.split;
+    ConvGemmArgs &a = dg.a;
     if (dgrad_pack) {   // images written by sf_op_conv1d_train_fwd: the fp32 matrix only if this launch reads it (the same predicate there)
       p.wd = const_cast<float *>(static_cast<const float *>(dgrad_pack));
       p.wdx = p.wd + (int64_t)C * taps * p.ldn;
@@ -139,6 +158,38 @@ int sf_op_conv1d_bwd_cl_p(int dtype, const float *x, const float *act, const flo
                           float *dx, float *dw, float *db, float *dgb, void *ws, int64_t ws_bytes, void *stream) {
   return conv1d_bwd_impl(dtype, x, act, stats, w, gamma, beta, groups, eps, dy, B, L, C, N, taps, pad, dx, dw, db, dgb, ws, ws_bytes, stream, dgrad_pack,
                          dx_add);
+}
+
+int sf_op_conv1d_bwd_variant(int dtype, int B, int L, int C, int N, int taps, int pad, char *label, int label_bytes) {
+  SF_API_BEGIN
+  if (!label || label_bytes < 1) fail(SF_ERR_INVALID, "sf_op_conv1d_bwd_variant: no room for the label");
+  label[0] = 0;
+  if (dtype != SF_F32 && dtype != SF_F32X) fail(SF_ERR_INVALID, "dtype must be SF_F32 or SF_F32X");
+  if (B < 1 || L < 1 || C < 1 || N < 1) fail(SF_ERR_INVALID, "sf_op_conv1d_bwd_variant: bad shape");
+  if (!bwd_geometry_ok(taps, pad)) fail(SF_ERR_UNSUPPORTED, "stride-1 'same' convolutions only (2 * pad == taps - 1)");
+  const bool x3 = dtype == SF_F32X;
+  const int64_t rows = (int64_t)B * L;
+  // dgrad: the arguments as conv1d_bwd_impl finishes them, a probe pointer wherever the entry hands over an image it packed
+  DgradPlan dg = dgrad_plan(x3, nullptr, B, L, C, N, taps, pad, nullptr);
+  const char *dname = "refused";
+  if (!dg.refused) {
+    dg.a.w = reinterpret_cast<const void *>(16);
+    if (dg.split) dg.a.wx = reinterpret_cast<const void *>(16);
+    if (!dg.direct && !conv_gemm_supported(F32, dg.a)) fail(SF_ERR_UNSUPPORTED, "no GEMM kernel takes this data gradient");
+    dname = dg.direct ? "conv_direct" : conv_gemm_variant_name(F32, dg.a);
+  }
+  // wgrad / bias grad: the same plan functions the launchers switch on
+  const ConvWgradPlan wp = conv_wgrad_plan(rows, C, N, taps, conv_wgrad_splits(rows, C, N, taps), x3 ? X3_BF16 : 0);
+  char wname[48];
+  if (wp.family == 0) snprintf(wname, sizeof wname, "wgrad_thin<1,%d>", wp.tq);
+  else snprintf(wname, sizeof wname, "%s<%d>/%s", wp.x3 ? "wgrad_x3" : "wgrad_lds", wp.family, wp.single_tap ? "tap" : "rows");
+  static const char *const reducers[] = {"direct", "vec", "scalar"};
+  static const char *const colsums[] = {"vec4", "vec1", "generic"};
+  const int n = snprintf(label, (size_t)label_bytes, "dgrad %s | %s S=%d %s | db %s Sb=%d", dname, wname, wp.S, reducers[wp.reducer],
+                         colsums[col_sums_variant(N)], bias_slices(rows, N));
+  if (n < 0 || n >= label_bytes) fail(SF_ERR_INVALID, "sf_op_conv1d_bwd_variant: the label needs %d bytes", n + 1);
+  return SF_OK;
+  SF_API_END
 }
 
 int64_t sf_op_gn_silu_train_stats_floats(int B, int L, int C, int groups) {

@@ -130,16 +130,19 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const ConvGemmArgs a) 
   }
 }
 
+// dynamic LDS of the kernel instantiated for nt output channels: the weights [K][nt], then the GroupNorm table
+size_t lds_bytes(const ConvGemmArgs &a, int nt) {
+  size_t b = (size_t)a.K * nt * sizeof(float);
+  if (a.pro == 1) {
+    int nb = min(a.M / a.Lout + 1, 256 / a.Lout + 2);
+    b += (size_t)nb * (a.cin + a.G) * sizeof(float2);
+  }
+  return b;
+}
+
 template <typename TI, typename TO> hipError_t go(const ConvGemmArgs &a, hipStream_t s) {
   size_t lds = 0;
-  auto lds_for = [&](int nt) {
-    size_t b = (size_t)a.K * nt * sizeof(float);
-    if (a.pro == 1) {
-      int nb = min(a.M / a.Lout + 1, 256 / a.Lout + 2);
-      b += (size_t)nb * (a.cin + a.G) * sizeof(float2);
-    }
-    return b;
-  };
+  auto lds_for = [&](int nt) { return lds_bytes(a, nt); };
   dim3 grid((a.M + 255) / 256);
 #define SF_GO(NT)                                                                                    \
   {                                                                                                  \
@@ -168,6 +171,13 @@ template <typename TI, typename TO> hipError_t go(const ConvGemmArgs &a, hipStre
 }
 
 }  // namespace
+
+bool conv_direct_supported(const ConvGemmArgs &a) {
+  if (a.geom != 0 || a.M <= 0 || a.n_store < 1 || a.n_store > 32) return false;
+  int nt = 1;
+  while (nt < a.n_store) nt *= 2;   // the instantiation go() picks
+  return lds_bytes(a, nt) <= 64 * 1024;
+}
 
 hipError_t launch_conv_direct(int dt_in, int dt_out, const ConvGemmArgs &a, hipStream_t s) {
   if (a.geom != 0 || a.M <= 0) return hipErrorInvalidValue;

@@ -255,6 +255,8 @@ hipError_t launch_cb_reduce_ln(int dt, const float *slab, int S, int B, int L, i
 // Same A/epilogue semantics as ConvGemmArgs (1-D geometry only); weights fp32 [N][taps*cin + cin2].
 // ---------------------------------------------------------------------------------------
 hipError_t launch_conv_direct(int dt_in, int dt_out, const ConvGemmArgs &a, hipStream_t s);
+// does launch_conv_direct take these arguments?  (at most 32 stored channels, the weights [K][channels] within 64 KiB of LDS)
+bool conv_direct_supported(const ConvGemmArgs &a);
 
 // GroupNorm partial statistics: x:(B*L, C) (row stride ld) -> slab [B][nch][G][2] = (mean, M2) per chunk of rows.
 struct GnPlan {
@@ -417,9 +419,22 @@ hipError_t launch_pack_train(const float *w, int N, int C, int taps, float *fw, 
 hipError_t launch_pack_train_many(const void *desc_dev, int n_items, int total_tiles, hipStream_t s);
 // dw (N, C, taps) = sum_rows dy[row][n] * act[row + t - pad][c];  partial: [S][N][taps*C] scratch, S = conv_wgrad_splits(...)
 int conv_wgrad_splits(int64_t rows, int C, int N, int taps);
+// the host-side decisions of launch_conv_wgrad for S row splits (the launcher switches on this; sf_op_conv1d_bwd_variant names it)
+enum { WGRAD_REDUCE_DIRECT = 0 /* one split: the kernel writes dw itself */, WGRAD_REDUCE_VEC = 1, WGRAD_REDUCE_SCALAR = 2 };
+struct ConvWgradPlan {
+  int family = 0;            // 0 = conv_wgrad_kernel<1, tq> (thin), 1 / 2 = the LDS-staged 64 x 64 / 128 x 128 tiles
+  bool x3 = false;           // conv_wgrad_x3_kernel<family> (split bf16 operands) instead of conv_wgrad_lds_kernel<family>
+  int tq = 0;                // thin kernel: 32-column tiles per workgroup (1 ... 3)
+  bool single_tap = false;   // LDS-staged kernels: single-tap staging (else whole rows plus halo)
+  int S = 1, rps = 0;        // row splits, rows per split (a multiple of 32: trailing splits may own no rows)
+  int reducer = WGRAD_REDUCE_DIRECT;
+};
+ConvWgradPlan conv_wgrad_plan(int64_t rows, int C, int N, int taps, int S, int x3);
+enum { COL_SUMS_VEC4 = 0, COL_SUMS_VEC1 = 1, COL_SUMS_GENERIC = 2 };
+int col_sums_variant(int cols);   // which kernel launch_col_sums_part takes for `cols` columns
 // x3: the products from split fp16 operands (both operands are activations: split while they are staged)
 // (bias_part / bias_slices / db: the bias gradient's slice sums, written by launch_col_sums_part BEFORE this call, are reduced by workgroups
-//  appended to the weight gradient's reducer; *bias_done tells whether that happened -- not with one row split or C % 4 != 0)
+//  appended to the weight gradient's reducer; *bias_done tells whether that happened -- not with one row split)
 hipError_t launch_conv_wgrad(const float *dy, const float *act, int B, int L, int C, int N, int taps, int pad, float *partial, int S, float *dw,
                              hipStream_t s, int x3_mode = 0, const float *bias_part = nullptr, int bias_slices = 0, float *db = nullptr,
                              bool *bias_done = nullptr);

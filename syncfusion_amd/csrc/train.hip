@@ -1124,29 +1124,54 @@ int conv_wgrad_splits(int64_t rows, int C, int N, int taps) {
   return (int)std::min<int64_t>(S, 512);   // >= 2 workgroups per CU; more splits only lengthen the reduction
 }
 
+// Every host-side decision of launch_conv_wgrad, made in one place: the launcher switches on it and sf_op_conv1d_bwd_variant names it.
+ConvWgradPlan conv_wgrad_plan(int64_t rows, int C, int N, int taps, int S, int x3) {
+  ConvWgradPlan p;
+  const int Q = taps * C;
+  p.S = S;
+  p.rps = (int)((rows + S - 1) / S);
+  p.rps = (p.rps + 31) / 32 * 32;
+  p.family = wgrad_family(C, N, taps);
+  // (the gradients dy span the whole fp32 exponent range: the bf16 split, whatever the forward pass uses)
+  p.x3 = x3 && p.family > 0;
+  // thin layers: one workgroup takes up to three 32-column tiles of (tap, channel) -- the three taps of a 32-channel level: dy is fetched
+  // once instead of once per tile, the activation rows of the taps overlap in the cache (same accumulation order per tile: same bits)
+  p.tq = p.family ? 0 : std::min((Q + 31) / 32, 3);
+  // the staging mode is the kernels' own choice (conv_wgrad_lds_kernel / conv_wgrad_x3_kernel, `single`), restated for the label only
+  p.single_tap = p.family > 0 && (taps == 1 || (C % (64 * p.family)) == 0);
+  // many slices of a small matrix (the thin levels: 512 row splits of 8 x 24 ... 32 x 96 outputs): eight threads per output walk the
+  // slices side by side; the vector kernel's thread walks ALL slices of its four outputs, 128 dependent round trips at 512 slices
+  // (35-45 us per launch, as much as the weight-gradient kernel itself)
+  const int64_t total = (int64_t)N * Q;
+  p.reducer = S == 1 ? WGRAD_REDUCE_DIRECT : (C % 4 == 0 && (S < 64 || total > 65536)) ? WGRAD_REDUCE_VEC : WGRAD_REDUCE_SCALAR;
+  return p;
+}
+
+int col_sums_variant(int cols) {
+  if (cols % 4 == 0 && cols <= 1024 && (256 % (cols / 4)) == 0) return COL_SUMS_VEC4;
+  if (cols <= 256 && (256 % cols) == 0) return COL_SUMS_VEC1;
+  return COL_SUMS_GENERIC;
+}
+
 hipError_t launch_conv_wgrad(const float *dy, const float *act, int B, int L, int C, int N, int taps, int pad, float *partial, int S, float *dw,
                              hipStream_t s, int x3, const float *bias_part, int bias_slices, float *db, bool *bias_done) {
   if (bias_done) *bias_done = false;
   const int rows = B * L, Q = taps * C;
-  int rps = (rows + S - 1) / S;
-  rps = (rps + 31) / 32 * 32;
-  float *direct = S == 1 ? dw : nullptr;
-  const int fam = wgrad_family(C, N, taps);
-  // (the gradients dy span the whole fp32 exponent range: the bf16 split, whatever the forward pass uses)
-  if (x3 && fam == 2)
+  const ConvWgradPlan pl = conv_wgrad_plan(rows, C, N, taps, S, x3);
+  const int rps = pl.rps, fam = pl.family;
+  float *direct = pl.reducer == WGRAD_REDUCE_DIRECT ? dw : nullptr;
+  if (pl.x3 && fam == 2)
     hipLaunchKernelGGL((conv_wgrad_x3_kernel<2, X3_BF16>), dim3((N + 127) / 128, (Q + 127) / 128, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
-  else if (x3 && fam == 1)
+  else if (pl.x3 && fam == 1)
     hipLaunchKernelGGL((conv_wgrad_x3_kernel<1, X3_BF16>), dim3((N + 63) / 64, (Q + 63) / 64, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
   else if (fam == 2)
     hipLaunchKernelGGL(conv_wgrad_lds_kernel<2>, dim3((N + 127) / 128, (Q + 127) / 128, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
   else if (fam == 1)
     hipLaunchKernelGGL(conv_wgrad_lds_kernel<1>, dim3((N + 63) / 64, (Q + 63) / 64, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
   else {
-    // thin layers: one workgroup takes up to three 32-column tiles of (tap, channel) -- the three taps of a 32-channel level: dy is fetched
-    // once instead of once per tile, the activation rows of the taps overlap in the cache (same accumulation order per tile: same bits)
     const int qt = (Q + 31) / 32;
-    if (qt >= 3) hipLaunchKernelGGL((conv_wgrad_kernel<1, 3>), dim3((N + 31) / 32, (qt + 2) / 3, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
-    else if (qt == 2) hipLaunchKernelGGL((conv_wgrad_kernel<1, 2>), dim3((N + 31) / 32, 1, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
+    if (pl.tq == 3) hipLaunchKernelGGL((conv_wgrad_kernel<1, 3>), dim3((N + 31) / 32, (qt + 2) / 3, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
+    else if (pl.tq == 2) hipLaunchKernelGGL((conv_wgrad_kernel<1, 2>), dim3((N + 31) / 32, 1, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
     else hipLaunchKernelGGL((conv_wgrad_kernel<1, 1>), dim3((N + 31) / 32, 1, S), dim3(256), 0, s, dy, act, rows, L, C, N, taps, pad, rps, partial, direct);
   }
   if (!direct) {
@@ -1159,10 +1184,7 @@ hipError_t launch_conv_wgrad(const float *dy, const float *act, int B, int L, in
       tail.cols = N;
       if (bias_done) *bias_done = true;
     }
-    // many slices of a small matrix (the thin levels: 512 row splits of 8 x 24 ... 32 x 96 outputs): eight threads per output walk the
-    // slices side by side; the vector kernel's thread walks ALL slices of its four outputs, 128 dependent round trips at 512 slices
-    // (35-45 us per launch, as much as the weight-gradient kernel itself)
-    if (C % 4 == 0 && (S < 64 || total > 65536)) {
+    if (pl.reducer == WGRAD_REDUCE_VEC) {
       const int nb = (int)((total / 4 + 255) / 256);
       hipLaunchKernelGGL(wgrad_reduce_vec_kernel, dim3((unsigned)(nb + tail.blocks())), dim3(256), 0, s, partial, S, N, C, taps, dw, nb, tail);
     } else {
@@ -1268,8 +1290,9 @@ hipError_t launch_length_sums(const float *x, const float *y, int B, int L, int 
 // gradient's reducer, launch_conv_wgrad)
 hipError_t launch_col_sums_part(const float *x, int64_t rows, int cols, float *part, int S, hipStream_t s) {
   const int64_t rps = (rows + S - 1) / S;
-  if (cols % 4 == 0 && cols <= 1024 && (256 % (cols / 4)) == 0) hipLaunchKernelGGL(col_sums_vec_kernel<4>, dim3(S), dim3(256), 0, s, x, rows, cols, rps, part);
-  else if (cols <= 256 && (256 % cols) == 0) hipLaunchKernelGGL(col_sums_vec_kernel<1>, dim3(S), dim3(256), 0, s, x, rows, cols, rps, part);
+  const int v = col_sums_variant(cols);
+  if (v == COL_SUMS_VEC4) hipLaunchKernelGGL(col_sums_vec_kernel<4>, dim3(S), dim3(256), 0, s, x, rows, cols, rps, part);
+  else if (v == COL_SUMS_VEC1) hipLaunchKernelGGL(col_sums_vec_kernel<1>, dim3(S), dim3(256), 0, s, x, rows, cols, rps, part);
   else hipLaunchKernelGGL(col_sums_kernel, dim3((cols + 63) / 64, S), dim3(64), 0, s, x, rows, cols, rps, part);
   return hipGetLastError();
 }
