@@ -393,6 +393,21 @@ int sf_op_resnet_mod_cb(int dtype, const void *x, const float *w1, const float *
                         const float *gn1_b, const float *gn2_g, const float *gn2_b, int groups, float eps_gn, const float *scale_shift,
                         float eps_ln, int B, int L, int C, int kb /* 128-channel blocks per workgroup: 1 or 2 */, void *h_out, void *m_out,
                         void *ws, int64_t ws_bytes, void *stream);
+/* The same item head at the 128-channel level (C = 128: one channel block is the whole reduction and the whole row), 16-bit dtypes,
+ * L a multiple of 32 and at most 1024: the convolutions finish their own results, no partial slab and no reducer launch --
+ *   gn_silu -> convolution [+ b1 -> h, GroupNorm chunk statistics of the stored h] -> convolution [GroupNorm+SiLU panel prologue from
+ *   those statistics; + b2 + x, LayerNorm over the row, Modulation -> m]
+ * and, with w_inj set, the InjectChannels GEMM the engine launches behind them:
+ *   z = m + Conv1x1(cat[m, ctx]) + b_inj (+ badd[b])     w_inj:(C, C + C2) fp32, ctx:(B, L, ctx_ld) in `dtype` (first C2 columns), badd:(B, C) or NULL
+ * h_out, m_out, z_out: (B, L, C) channels-last in `dtype` (h_out, and m_out when z_out is asked for, optional).  stats_out (optional):
+ * (B, nch, groups, 2) floats = (mean, M2) of h per chunk and group, as the second convolution reads them: chunks of 8 rows up to
+ * L = 256, 16 up to 512, 32 beyond (nch = L / rows), the chunking and the bits of sf_op_resnet_mod_cb's reducer.
+ * SF_ERR_UNSUPPORTED, before anything is launched, outside that coverage (fp32 / fp32x, C != 128, other L). */
+int64_t sf_op_resnet_mod_cbd_workspace_bytes(int B, int L, int C, int C2);
+int sf_op_resnet_mod_cbd(int dtype, const void *x, const float *w1, const float *b1, const float *w2, const float *b2, const float *gn1_g,
+                         const float *gn1_b, const float *gn2_g, const float *gn2_b, int groups, float eps_gn, const float *scale_shift,
+                         float eps_ln, int B, int L, int C, const float *w_inj, const float *b_inj, const void *ctx, int ctx_ld, int C2,
+                         const float *badd, void *h_out, void *m_out, void *z_out, float *stats_out, void *ws, int64_t ws_bytes, void *stream);
 /* InjectChannels followed by the attention pre-norm projection, as the engine chains the two GEMMs of an item (a-unet InjectChannelsItem
  * + the LayerNorm / to_q | to_kv Linear of AttentionItem), 16-bit dtypes:
  *   z = m + Conv1x1(cat[m, ctx]) + b_inj            m:(B,L,C), ctx:(B,L,C2) channels-last in `dtype`; w_inj:(C, C + C2) fp32

@@ -576,6 +576,114 @@ int sf_op_resnet_mod_cb(int dtype, const void *x, const float *w1, const float *
   SF_API_END
 }
 
+int64_t sf_op_resnet_mod_cbd_workspace_bytes(int B, int L, int C, int C2) {
+  if (B < 1 || L < 1 || C < 1 || C2 < 0) return -1;
+  Workspace dry(nullptr, 0);
+  const int64_t M = (int64_t)B * L;
+  dry.alloc(2 * (int64_t)C * C * 3 * 2);     // the two fragment-ordered convolution weights
+  dry.alloc(M * C * 2);                      // SiLU(GroupNorm(x))
+  dry.alloc(M * C * 2);                      // h (when the caller does not ask for it)
+  dry.alloc(M * C * 2);                      // m (likewise)
+  dry.alloc((int64_t)B * 32 * 64 * 2 * 4);   // chunk statistics (likewise)
+  dry.alloc((int64_t)C * (C + C2) * 2);      // InjectChannels weights
+  return dry.used();
+}
+
+int sf_op_resnet_mod_cbd(int dtype, const void *x, const float *w1, const float *b1, const float *w2, const float *b2, const float *gn1_g,
+                         const float *gn1_b, const float *gn2_g, const float *gn2_b, int groups, float eps_gn, const float *scale_shift, float eps_ln,
+                         int B, int L, int C, const float *w_inj, const float *b_inj, const void *ctx, int ctx_ld, int C2, const float *badd,
+                         void *h_out, void *m_out, void *z_out, float *stats_out, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!x || !w1 || !b1 || !w2 || !b2 || !gn1_g || !gn1_b || !gn2_g || !gn2_b || !ws) fail(SF_ERR_INVALID, "null argument");
+  if (!m_out && !(w_inj && z_out)) fail(SF_ERR_INVALID, "no output requested");
+  if (w_inj && (!b_inj || !z_out || C2 < 0 || (C2 > 0 && (!ctx || ctx_ld < C2)))) fail(SF_ERR_INVALID, "InjectChannels operands incomplete");
+  // every refusal comes before the first launch: a refused call writes nothing
+  if (groups < 1 || groups > 64 || !conv_cb_direct_ok(dtype, B, L, C, C, groups))
+    fail(SF_ERR_UNSUPPORTED, "shape outside the direct channel-block epilogues' coverage (16-bit, C = 128, L a multiple of 32, L <= 1024)");
+  const int64_t M = (int64_t)B * L;
+  ConvGemmArgs ai;   // InjectChannels on the modulated rows: the plain GEMM, as the engine launches it behind the direct chain
+  if (w_inj) {
+    if (C2 % 32 || ctx_ld % 8) fail(SF_ERR_UNSUPPORTED, "C2 must be a multiple of 32 and ctx_ld of 8");
+    ai.src_ld = C;
+    ai.src2 = C2 ? ctx : nullptr;
+    ai.src2_ld = ctx_ld;
+    ai.bias = b_inj;
+    ai.M = (int)M;
+    ai.N = ai.n_store = C;
+    ai.K = C + C2;
+    ai.cin = C;
+    ai.cin2 = C2;
+    ai.taps = 1;
+    ai.Lout = ai.Lsrc = L;
+    ai.out = z_out;
+    ai.out_ld = C;
+    ai.res_ld = C;
+    ai.short_k = 1;
+    if (badd) {
+      ai.badd = badd;
+      ai.badd_ld = C;
+    }
+  }
+  const int64_t need = sf_op_resnet_mod_cbd_workspace_bytes(B, L, C, w_inj ? C2 : 0);
+  if (need < 0 || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  Workspace wk(ws, ws_bytes);
+  const int64_t es = 2;
+  char *wp = static_cast<char *>(wk.alloc(2 * (int64_t)C * C * 3 * es));
+  void *wp1 = wp, *wp2 = wp + (int64_t)C * C * 3 * es;
+  void *act = wk.alloc(M * C * es);
+  void *h = h_out ? h_out : wk.alloc(M * C * es);
+  void *m = m_out ? m_out : wk.alloc(M * C * es);
+  float *stats = stats_out ? stats_out : static_cast<float *>(wk.alloc((int64_t)B * 32 * 64 * 2 * 4));
+  if (w_inj) {
+    void *wi = wk.alloc((int64_t)C * (C + C2) * es);
+    ai.w = wi;
+    ai.src = ai.res = m;
+    if (!conv_gemm_supported(dtype, ai)) fail(SF_ERR_UNSUPPORTED, "InjectChannels shape outside the GEMM kernels' coverage");
+    SF_HIP(launch_pack_rows(dtype, w_inj, C, C + C2, C + C2, nullptr, wi, C + C2, s));
+  }
+  SF_HIP(launch_pack_conv_cb(dtype, w1, C, C, wp1, s));
+  SF_HIP(launch_pack_conv_cb(dtype, w2, C, C, wp2, s));
+  SF_HIP(launch_gn_silu(dtype, x, C, B, L, C, groups, gn1_g, gn1_b, eps_gn, act, C, s));
+  ConvCbArgs a;
+  a.src = act;
+  a.src_ld = C;
+  a.wp = wp1;
+  a.B = B;
+  a.L = L;
+  a.C = a.N = C;
+  a.G = groups;
+  const CbGnPlan gp = cb_gn_plan(L);
+  a.nch = gp.nch;
+  a.chunk_rows = gp.chunk_rows;
+  a.epi = 1;   // direct_gn: h and its chunk statistics
+  a.out = h;
+  a.out_ld = C;
+  a.bias = b1;
+  a.stats_out = stats;
+  SF_HIP(launch_conv_cb(dtype, a, s));
+  a.src = h;
+  a.wp = wp2;
+  a.pro = 1;
+  a.stats = stats;
+  a.gamma = gn2_g;
+  a.beta = gn2_b;
+  a.eps = eps_gn;
+  a.epi = 2;   // direct_ln: + bias + x, LayerNorm, Modulation
+  a.out = m;
+  a.bias = b2;
+  a.stats_out = nullptr;
+  a.res = x;
+  a.res_ld = C;
+  a.ss = scale_shift;
+  a.ss_ld = 2 * C;
+  a.eps_ln = eps_ln;
+  SF_HIP(launch_conv_cb(dtype, a, s));
+  if (w_inj) SF_HIP(launch_conv_gemm(dtype, ai, s));
+  return SF_OK;
+  SF_API_END
+}
+
 int64_t sf_op_inject_prenorm_proj_workspace_bytes(int B, int L, int C, int C2, int N) {
   if (B < 1 || L < 1 || C < 32 || C2 < 0 || N < 8) return -1;
   const int64_t M = (int64_t)B * L, K1 = C + (C2 + 31) / 32 * 32;

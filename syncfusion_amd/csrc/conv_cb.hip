@@ -76,9 +76,19 @@ __device__ __forceinline__ float2 merge_parts(const float2 (&cs)[4], const float
 // x * L < 2^32): the weight loads are issued ~100 instructions into the kernel, not ~400.
 // KB = 128-channel blocks per workgroup (1 or 2): two blocks halve the number of partial slabs (their traffic is what limits the chain at
 // 8-16 clips per branch) for twice the weight stream per workgroup (48 fragments per wave).
-template <typename T, int MT, bool PRO, int KB>
+// EPI = what becomes of the accumulators (kernels.h, ConvCbArgs::epi).  0: fp32 partial slab.  With ONE channel slice (C = N = 128, KB = 1) the
+// workgroup holds the full reduction of whole rows, L % 32 == 0 makes every 32-row MFMA tile one statistics chunk of one clip, and the reducer
+// launches have nothing left to sum:
+//   1 (direct_gn): h = acc + bias -> 16-bit, and the (mean, M2) GroupNorm chunk statistics of the STORED values in the layout pro 1 reads,
+//                  chunked and summed exactly as cb_reduce_gn does it (the rounded tile goes through LDS: the panel is free by then).
+//   2 (direct_ln): y = acc + bias + residual; row mean, then squares about it, over the four waves through LDS (the panel is free after the
+//                  MFMA loop) in cb_reduce_ln's summation order; LayerNorm + Modulation -> 16-bit, the chain's m bit for bit.
+// Their operands (bias, residual rows, scale / shift of the tile's clip) are requested behind the weight loads.
+template <typename T, int MT, bool PRO, int KB, int EPI = 0>
 __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const int mtiles, const unsigned bytes_src) {
   using frag = typename Frag16<T>::type;
+  using v4 = T __attribute__((ext_vector_type(4)));
+  static_assert(EPI == 0 || (KB == 1 && MT <= 2), "direct epilogues: one channel block, at most two row tiles");
   constexpr int KCW = KC * KB, PITCHW = KCW + 8, TPR = KCW / 8, RPP = 256 / TPR;   // channels per workgroup, LDS pitch, threads per row, rows per pass
   constexpr int BM = 32 * MT, PR = BM + 2, NV = (PR + RPP - 1) / RPP;
   __shared__ __attribute__((aligned(16))) T panel[PR * PITCHW];
@@ -160,6 +170,33 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
     for (int s = 0; s < 24; ++s) wf[blk * 24 + s] = wp[s * 64 + lane];
   }
   __builtin_amdgcn_sched_barrier(0);
+  // ---- 3b. operands of the direct epilogues, behind the weights: a lane ends up with columns 32 wave + 8 g + 4 fh + 0..3 (g = 0..3) of row fr
+  //          of each tile.  Every address is valid whatever the tile (rows clamped, no Modulation: the bias vector stands in), no branch ----
+  const int fr = lane & 31, fh = lane >> 5;
+  const int ec0 = wave * 32 + 4 * fh;
+  f32x4 eb[4], esc[MT][4], esh[MT][4];
+  v4 er[MT][4];
+  if constexpr (EPI != 0) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) eb[g] = *reinterpret_cast<const f32x4 *>(a.bias + ec0 + 8 * g);
+  }
+  if constexpr (EPI == 2) {
+    const float *ssp = a.ss ? a.ss : a.bias;
+    const int sh_off = a.ss ? a.N : 0;
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const int m = min(r0 + t * 32 + fr, M - 1);
+      const T *rp = static_cast<const T *>(a.res) + (size_t)m * a.res_ld + ec0;
+      const float *sp = ssp + (a.ss ? (size_t)divL(min(r0 + t * 32, M - 1)) * a.ss_ld : 0) + ec0;   // the tile lies inside one clip
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        er[t][g] = *reinterpret_cast<const v4 *>(rp + 8 * g);
+        esc[t][g] = *reinterpret_cast<const f32x4 *>(sp + 8 * g);
+        esh[t][g] = *reinterpret_cast<const f32x4 *>(sp + sh_off + 8 * g);
+      }
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
   // (the compiler otherwise hoists the first use of a chunk sum in front of the weight loads, and its wait with it)
   if constexpr (PRO) {
 #pragma unroll
@@ -199,7 +236,6 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   __syncthreads();
   // ---- 6. D^T[n][m] += W[n][k] * act[m + tap - 1][k]: the weight fragment is the MFMA's A operand, so a lane ends up with four
   //         consecutive output COLUMNS of one row (16-byte slab stores) ---------------------------------------------------------
-  const int fr = lane & 31, fh = lane >> 5;
   bool ok0[MT], ok2[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
@@ -226,6 +262,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
           if (tap == 2) af = ok2[t] ? af : zf;
           acc[t] = mfma32x16(wf[blk * 24 + tap * 8 + ks], af, acc[t]);
         }
+  if constexpr (EPI == 0) {
   // ---- 7. partial slab ---------------------------------------------------------------------------------------------------------
   float *sl = a.slab + (size_t)cb * M * a.N + nt * 128 + wave * 32 + 4 * fh;
 #pragma unroll
@@ -238,6 +275,158 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
         *reinterpret_cast<f32x4 *>(sl + (unsigned)(m * a.N + 8 * g)) = v;
       }
     }
+  }
+  } else if constexpr (EPI == 1) {
+  // ---- 7a. direct_gn: h = acc + bias -> 16-bit; chunk statistics of the stored values.  M % 32 == 0: a tile is whole or absent.  The rounded
+  //          tile goes through LDS (the panel is free) and the statistics are formed by cb_reduce_gn's threads in cb_reduce_gn's order, per chunk
+  //          of a.chunk_rows = 8 P rows (cb_gn_plan: 8, 16 or 32, whole chunks per tile): the same bits as the chain's, so the convolution
+  //          that merges them sees the same (mean, rstd) ----------------------------------------------------------------------------------
+  __syncthreads();   // every wave has read its last panel fragment
+  T *tile = panel;                                                  // [BM][128]
+  float *red = reinterpret_cast<float *>(panel + BM * 128);         // [4 waves][8 groups][2 passes], then the group means [8]
+  float *gmean = red + 64;
+  static_assert(BM * 128 * sizeof(T) + 72 * sizeof(float) <= PR * PITCHW * sizeof(T), "tile + reduction scratch fit the panel");
+  T *outp = static_cast<T *>(a.out) + ec0;
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = r0 + t * 32 + fr;
+    const bool live = r0 + t * 32 < M;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      v4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = from_f<T>(acc[t][4 * g + e] + eb[g][e]);
+      if (live) *reinterpret_cast<v4 *>(outp + (size_t)m * a.out_ld + 8 * g) = o;
+      *reinterpret_cast<v4 *>(tile + (t * 32 + fr) * 128 + ec0 + 8 * g) = o;
+    }
+  }
+  __syncthreads();
+  {
+    const int R = a.chunk_rows, P = R >> 3;
+    const int cq = tid & 31, rr = tid >> 5;            // thread = 4 consecutive columns of one row per pass, as in cb_reduce_gn
+    const int cpg = 1 << a.log2cpg, span = cpg >> 2, gpb = KC >> a.log2cpg;
+    auto group_total = [&](float tt, int k) {
+      for (int off = 1; off < span; off <<= 1) tt += __shfl_xor(tt, off, 64);
+      tt += __shfl_xor(tt, 32, 64);
+      if (lane < 32 && (cq % span) == 0) red[(wave * 8 + cq / span) * 2 + k] = tt;
+      __syncthreads();
+      float x = 0.f;
+      if (tid < gpb) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) x += red[(w * 8 + tid) * 2 + k];
+      }
+      return x;
+    };
+    for (int ch = 0; ch < BM / R; ++ch) {
+      const int m0 = r0 + ch * R;
+      float xs[4][4];
+      float s1 = 0.f;
+#pragma unroll
+      for (int pp = 0; pp < 4; ++pp)
+        if (pp < P) {
+          const v4 v = *reinterpret_cast<const v4 *>(tile + (ch * R + pp * 8 + rr) * 128 + cq * 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            xs[pp][e] = to_f(v[e]);
+            s1 += xs[pp][e];
+          }
+        }
+      const float a1 = group_total(s1, 0);
+      if (tid < gpb) gmean[tid] = a1 / ((float)R * (float)cpg);
+      __syncthreads();
+      const float mu = gmean[cq / span];
+      float s2 = 0.f;
+#pragma unroll
+      for (int pp = 0; pp < 4; ++pp)
+        if (pp < P) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float d = xs[pp][e] - mu;
+            s2 = fmaf(d, d, s2);
+          }
+        }
+      const float a2 = group_total(s2, 1);
+      if (tid < gpb && m0 < M) {
+        const int clip = divL(m0), kc = (m0 - clip * a.L) / R;
+        float *o = a.stats_out + ((size_t)(clip * a.nch + kc) * gpb + tid) * 2;
+        o[0] = gmean[tid];
+        o[1] = a2;
+      }
+      __syncthreads();   // red / gmean serve the next chunk
+    }
+  }
+  } else {
+  // ---- 7b. direct_ln: y = acc + bias + residual; LayerNorm over the 128 columns of the row (four waves, through LDS), Modulation ------------
+  //          The row sums take cb_reduce_ln's order -- a column quad's (y0 + y1) + (y2 + y3), then the 32 quads paired by the bits of the
+  //          quad index from the top (wave, then g, then fh) -- so that m is the chain's m bit for bit.  Every lane of a row adds the row's 32
+  //          quad sums itself: LDS [pass][row][16-byte slot fh * 4 + wave, XOR row % 8 against bank conflicts][g].
+  __syncthreads();   // every wave has read its last panel fragment: the panel's memory carries the quad sums
+  float *red = reinterpret_cast<float *>(panel);
+  static_assert(2 * BM * 32 * sizeof(float) <= PR * PITCHW * sizeof(T), "the quad sums of both passes fit the panel");
+  T *outp = static_cast<T *>(a.out) + ec0;
+  const int myslot = (fh * 4 + wave) ^ (fr & 7);
+  auto row_total = [&](const float *rowp) {
+    float tot[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f32x4 v[4];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) v[w] = *reinterpret_cast<const f32x4 *>(rowp + (((h * 4 + w) ^ (fr & 7)) << 2));
+      float u[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) u[g] = (v[0][g] + v[2][g]) + (v[1][g] + v[3][g]);
+      tot[h] = (u[0] + u[2]) + (u[1] + u[3]);
+    }
+    return tot[0] + tot[1];
+  };
+  float y[MT][16];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    f32x4 p;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y[t][4 * g + e] = (acc[t][4 * g + e] + eb[g][e]) + to_f(er[t][g][e]);
+      p[g] = (y[t][4 * g] + y[t][4 * g + 1]) + (y[t][4 * g + 2] + y[t][4 * g + 3]);
+    }
+    *reinterpret_cast<f32x4 *>(red + (t * 32 + fr) * 32 + (myslot << 2)) = p;
+  }
+  __syncthreads();
+  float mean[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    mean[t] = row_total(red + (t * 32 + fr) * 32) / 128.0f;
+    f32x4 q;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      q[g] = 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = y[t][4 * g + e] - mean[t];
+        q[g] = fmaf(d, d, q[g]);
+      }
+    }
+    *reinterpret_cast<f32x4 *>(red + (BM + t * 32 + fr) * 32 + (myslot << 2)) = q;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = r0 + t * 32 + fr;
+    const float rstd = rsqrtf(row_total(red + (BM + t * 32 + fr) * 32) / 128.0f + a.eps_ln);
+    if (m < M) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        v4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float z = (y[t][4 * g + e] - mean[t]) * rstd;
+          if (a.ss) z = fmaf(z, 1.0f + esc[t][g][e], esh[t][g][e]);
+          o[e] = from_f<T>(z);
+        }
+        *reinterpret_cast<v4 *>(outp + (size_t)m * a.out_ld + 8 * g) = o;
+      }
+    }
+  }
   }
 }
 
@@ -633,6 +822,13 @@ bool conv_cb_tile_stats_ok(int L, int C, int G) {
   return ((L + 30) / 32 + 1) * (cpg / 32) <= 32;
 }
 
+// the direct epilogues (ConvCbArgs::epi): one channel slice and whole rows per workgroup, a 32-row MFMA tile = one statistics chunk inside one clip
+bool conv_cb_direct_ok(int dt, int B, int L, int C, int N, int G) {
+  if (dt != BF16 && dt != F16) return false;
+  if (C != KC || N != KC || (L % 32) || L / 32 > 32) return false;
+  return conv_cb_shape_ok(dt, B, L, C, N, G);
+}
+
 // Measured alone on the chip (tools/cb_bench.py, profiles/r4_a_cb_bench.txt; HBM-cold weights, us per launch, MT = 1 / 2 / 3 / 4):
 //   d7 (176 rows, C 1024): 6.7 / 6.4 / 8.2 / 8.6     d6 (352 rows): 8.9 / 8.5 / 9.2 / 9.3     d5 (704 rows, C 512): 6.0 / 6.1 / 7.8 / 8.2
 //   d4 (1408 rows, C 256): 4.0 / 5.1 / 6.8 / 7.1   (88 workgroups at MT = 2)
@@ -664,18 +860,29 @@ hipError_t launch_conv_cb(int dt, const ConvCbArgs &a0, hipStream_t s) {
   if (a0.pro == 2 && !conv_cb_tile_stats_ok(a0.L, a0.C, a0.G)) return hipErrorInvalidValue;
   ConvCbArgs a = a0;
   if (dt == F32X && a.kb == 2) return hipErrorInvalidValue;   // one channel block per workgroup in the split-operand form
+  if (a.epi) {
+    // direct_gn after a materialised GroupNorm+SiLU (pro 0), direct_ln behind the chunk statistics it left (pro 1): the two instantiated forms
+    if (!((a.epi == 1 && a.pro == 0) || (a.epi == 2 && a.pro == 1)) || a.kb == 2) return hipErrorInvalidValue;
+    if (!conv_cb_direct_ok(dt, a.B, a.L, a.C, a.N, a.G) || a.G < 1) return hipErrorInvalidValue;
+    if (!a.out || !a.bias || (a.out_ld % 4) || a.out_ld < a.N) return hipErrorInvalidValue;
+    if (a.epi == 1 && !a.stats_out) return hipErrorInvalidValue;
+    if (a.epi == 2 && (!a.res || (a.res_ld % 4) || a.res_ld < a.N)) return hipErrorInvalidValue;
+    if (a.epi == 2 && a.ss && ((a.ss_ld % 4) || (reinterpret_cast<uintptr_t>(a.ss) % 16))) return hipErrorInvalidValue;
+    // statistics chunks (written by epi 1, read by pro 1): whole chunks of 8, 16 or 32 rows per tile, cb_gn_plan's choice
+    if ((a.chunk_rows != 8 && a.chunk_rows != 16 && a.chunk_rows != 32) || a.nch * a.chunk_rows != a.L || a.nch > 32) return hipErrorInvalidValue;
+  }
   const int kb = a.kb == 2 ? 2 : 1;
   const int M = a.B * a.L, S = a.C / KC / kb;   // partial slabs = workgroups along the input channels
   if (kb == 2 && ((a.C / KC) % 2 || (a.pro && a.C / a.G < 32))) return hipErrorInvalidValue;   // <= 8 groups inside a 256-channel range
   a.log2S = 0;
   while ((1 << a.log2S) < S) ++a.log2S;
-  const int cpg = a.pro ? a.C / a.G : KC;
+  const int cpg = (a.pro || a.epi == 1) ? a.C / a.G : KC;   // (direct_gn without prologue: the groups of its OUTPUT, N = C)
   a.log2cpg = 0;
   while ((1 << a.log2cpg) < cpg) ++a.log2cpg;
   if ((1 << a.log2S) != S || (1 << a.log2cpg) != cpg) return hipErrorInvalidValue;
   a.magicL = (unsigned)((0x100000000ull + (unsigned)a.L - 1) / (unsigned)a.L);   // x / L == mulhi(x, magicL) while x * L < 2^32
   int mt = kb == 2 ? std::min(2, conv_cb_mt(M, a.N, a.C / 2)) : conv_cb_mt(M, a.N, a.C);
-  if (dt == F32X) mt = std::min(mt, 2);
+  if (dt == F32X || a.epi) mt = std::min(mt, 2);
   const int mtiles = (M + 32 * mt - 1) / (32 * mt), nws = (a.N / 128) * S;
   const int pf_rows = (a.pf.ptr && a.pf.bytes >= 16 && a.pf.wgs > 0) ? (a.pf.wgs + nws - 1) / nws : 0;
   a.pf.wgs = pf_rows * nws;
@@ -689,6 +896,22 @@ hipError_t launch_conv_cb(int dt, const ConvCbArgs &a0, hipStream_t s) {
       if (mt == 1) hipLaunchKernelGGL((conv_cb_x3_kernel<1, false>), grid, dim3(256), 0, s, a, mtiles, bytes_src);
       else hipLaunchKernelGGL((conv_cb_x3_kernel<2, false>), grid, dim3(256), 0, s, a, mtiles, bytes_src);
     }
+    return hipGetLastError();
+  }
+  if (a.epi) {
+#define SF_CBD(T, MT)                                                                                                          \
+  do {                                                                                                                         \
+    if (a.epi == 1) hipLaunchKernelGGL((conv_cb_kernel<T, MT, false, 1, 1>), grid, dim3(256), 0, s, a, mtiles, bytes_src);     \
+    else hipLaunchKernelGGL((conv_cb_kernel<T, MT, true, 1, 2>), grid, dim3(256), 0, s, a, mtiles, bytes_src);                 \
+  } while (0)
+    if (dt == BF16) {
+      if (mt == 1) SF_CBD(bf16, 1);
+      else SF_CBD(bf16, 2);
+    } else {
+      if (mt == 1) SF_CBD(f16, 1);
+      else SF_CBD(f16, 2);
+    }
+#undef SF_CBD
     return hipGetLastError();
   }
 #define SF_CB2(T, MT, KB_)                                                                                                \

@@ -492,7 +492,7 @@ static const char *variant_name_bf16(int dt, const ConvGemmArgs &a) {
   static const char *fast_names[2][3] = {{"conv_gemm_fast<f32,64x64>", "conv_gemm_fast<f32,64x32>", "conv_gemm_fast<f32,32x32>"},
                                          {"conv_gemm_fast<bf16,64x64>", "conv_gemm_fast<bf16,64x32>", "conv_gemm_fast<bf16,32x32>"}};
   const long t64 = (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64);
-  const bool short_act = t64 < short_act_tiles() && a.K >= 256 && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
+  const bool short_act = t64 < short_act_tiles() && a.K >= (a.short_k ? 128 : 256) && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
   if (!short_act) {
     V2Plan pl;
     if (conv_gemm_v2_plan(dt, a, pl)) return conv_gemm_v2_name(dt, pl);
@@ -531,7 +531,7 @@ bool conv_gemm_emits_rowpart(int dt, const ConvGemmArgs &a) {
   }
   if ((a.n_store % 32) || a.n_store != a.N) return false;
   const long t64 = (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64);
-  const bool short_act = t64 < short_act_tiles() && a.K >= 256 && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
+  const bool short_act = t64 < short_act_tiles() && a.K >= (a.short_k ? 128 : 256) && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
   if (!(short_act || use_sk(a))) return false;                 // would go to v2 / the classic tiles
   if ((a.cin % 32) || (a.cin2 % 32) || (a.K % 32)) return false;
   if (conv_gemm_sk_variant(a) != 2) return false;              // 32x32 tiles only
@@ -554,7 +554,7 @@ hipError_t launch_conv_gemm(int dt, const ConvGemmArgs &a, hipStream_t s) {
   if (f.path == 6) return launch_conv_gemm_mt(dt, a, s);
   if (f.path == 0 && conv_gemm_mt_wanted(dt, a)) return launch_conv_gemm_mt(dt, a, s);
   const long t64 = (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64);
-  const bool short_act = t64 < short_act_tiles() && a.K >= 256 && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
+  const bool short_act = t64 < short_act_tiles() && a.K >= (a.short_k ? 128 : 256) && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
   if (f.path == 4 || (f.path == 0 && !short_act)) {
     V2Plan pl;   // long activations: classic 2x2-wave tiles, channel counts that are multiples of 64, no prologue
     if (conv_gemm_v2_plan(dt, a, pl)) return launch_conv_gemm_v2(dt, a, pl, s);

@@ -85,6 +85,9 @@ struct ConvGemmArgs {
   // epilogue: v = acc + bias; v *= bscale[b][n]; v += res[m][n]; v += badd[b][n]; v = act(v)
   //   act: 0 none, 1 relu, 2 gelu(erf), 3 silu(gelu(v))   out_f32: store fp32 whatever the compute type
   int badd_ld = 0, bscale_ld = 0, act = 0, out_f32 = 0;
+  // caller's hint: a short reduction (128 <= K < 256) on short activations still takes the small-batch 32x32 family instead of the classic
+  // 64x64 tile -- the InjectChannels GEMM (K = 160) behind the direct channel-block chain: 352 workgroups instead of 88
+  int short_k = 0;
   // Row-LayerNorm fusion (conv_gemm_fast / conv_gemm_wp, 32x32 tiles only):
   //   producer side: rowpart_out != nullptr -> the epilogue also writes, per output row and 32-column tile, the (mean, M2)
   //     of the STORED values: rowpart_out[(m * rowpart_nt + n_tile) * 2 + {0,1}]   (rowpart_nt = n_store / 32);
@@ -231,6 +234,19 @@ struct ConvCbArgs {
   const float *gamma = nullptr, *beta = nullptr, *stats = nullptr;
   float eps = 1e-5f;
   int kb = 1;   // 128-channel blocks per workgroup: 1, or 2 (slab[C / 256][M][N]: half the partial slabs, twice the weight stream per workgroup)
+  // Direct epilogues: with ONE channel slice (C = N = 128, kb = 1) the workgroup's accumulators are the result and no slab is written.
+  // They need L % 32 == 0 and L <= 1024 (a 32-row MFMA tile lies inside one clip and holds whole statistics chunks); launch_conv_cb
+  // returns hipErrorInvalidValue for anything else (conv_cb_direct_ok).
+  //   epi 1 (pro 0): out = acc + bias (16-bit) and the GroupNorm chunk statistics of the STORED values -> stats_out [B][nch][G][2]
+  //                  = (mean, M2) per chunk of chunk_rows rows, nch * chunk_rows = L (cb_gn_plan(L): what cb_reduce_gn writes, bit for bit)
+  //   epi 2 (pro 1): y = acc + bias + res;  out = LayerNorm_N(y; eps_ln) * (1 + ss[b][n]) + ss[b][N + n]  (ss null: the plain normalised rows)
+  int epi = 0;
+  void *out = nullptr;
+  const float *bias = nullptr, *ss = nullptr;
+  const void *res = nullptr;
+  float *stats_out = nullptr;
+  int out_ld = 0, res_ld = 0, ss_ld = 0;
+  float eps_ln = 1e-6f;
   // filled by the launcher: log2(C / 128), log2(C / G), ceil(2^32 / L)
   int log2S = 0, log2cpg = 7;
   unsigned magicL = 0;
@@ -240,6 +256,7 @@ struct CbGnPlan {
 };
 bool conv_cb_shape_ok(int dt, int B, int L, int C, int N, int G);
 bool conv_cb_tile_stats_ok(int L, int C, int G);   // pro 2 applicable
+bool conv_cb_direct_ok(int dt, int B, int L, int C, int N, int G);   // the direct epilogues (ConvCbArgs::epi) take this geometry
 int conv_cb_mt(int M, int N, int C);            // 32-row tiles per workgroup the launcher picks
 size_t conv_cb_weight_elems(int N, int C);
 hipError_t launch_pack_conv_cb(int dt, const float *w /* (N, C, 3) fp32 */, int N, int C, void *out, hipStream_t s);

@@ -52,6 +52,7 @@ struct Level {
   void *qkv = nullptr, *ao = nullptr, *ctx = nullptr, *act = nullptr;
   bool cb = false;   // the item heads of this level run as the channel-block split-K chain (conv_cb.hip)
   int cb_kb = 1;     // ... with this many 128-channel blocks per workgroup (2 halves the partial slabs)
+  bool cbd = false;  // C = 128: the item's convolutions run on conv_cb's direct epilogues (one channel slice: no slab, no reducer launch)
 };
 
 struct Plan {  // everything carved out of the caller's workspace for one (B, L0, two_pass)
@@ -722,6 +723,13 @@ Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num
         l.cb = true;   // two channel blocks per workgroup: half the slabs (8-16 clips per branch at the 1024-channel levels)
         l.cb_kb = 2;
       }
+      // The 128-channel level: one channel block is the whole reduction and the whole row, so the convolutions finish h (+ its GroupNorm chunk
+      // statistics) and m themselves (ConvCbArgs::epi) -- four launches per item instead of five, no slab.  Up to 2816 rows per branch (the
+      // batch-8 step, 88 workgroups); longer activations fill the chip on the macro tiles and stay there.
+      static const bool no_cbd = tune_env("SF_NO_CB_DIRECT") != nullptr;   // A/B aid: keep gn_silu -> GEMM -> gn_silu -> GEMM -> LN-folded InjectChannels
+      static const int cbd_max_rows = 2816;
+      l.cbd = !l.cb && !no_cbd && !u.x3 && have_w && l.C == 128 && rows <= cbd_max_rows && conv_cb_direct_ok(u.dt, bt, l.L, l.C, l.C, c.resnet_groups) &&
+              (int64_t)bt * 32 * c.resnet_groups * 2 <= p.slab_half;
       if (l.cb) need = std::max<int64_t>(need, (int64_t)(l.C / 128 / l.cb_kb) * rows * l.C);
       if (l.cb) need_gp = std::max<int64_t>(need_gp, ((rows + 31) / 32) * (l.C / 32) * 4);
     }
@@ -1037,6 +1045,8 @@ struct Exec {
       fuse_mod = conv_gemm_emits_rowpart(u.dt, filled(g.conv2, pc)) && conv_gemm_ln_ok(u.dt, filled(g.inject, pi));
     }
     const bool use_cb = l.cb && !fuse_act && g.conv1.wcb && g.conv2.wcb && g.conv1.bias && g.conv2.bias && p.cbslab;
+    const bool use_cbd = l.cbd && !use_cb && !fuse_act && g.conv1.wcb && g.conv2.wcb && g.conv1.bias && g.conv2.bias && g.conv1.cin == C &&
+                         (g.mod_off % 4) == 0 && (p.mod_stride % 4) == 0;   // (16-byte loads of the Modulation pair)
     bool fuse_attn = false;
     if (g.attn && C % 32 == 0 && !u.no_ln_fusion) {
       ConvGemmArgs pq = qkv_args(tB);
@@ -1045,9 +1055,10 @@ struct Exec {
       pq.ln_eps = 1e-5f;
       pq.ln_colsum = g.qkv_colsum;
       ConvGemmArgs pi = inject_args(tA, tB);
+      pi.short_k = use_cbd ? 1 : 0;
       // the LN-folded InjectChannels kernel always writes row partials; the channel-block chain launches the PLAIN InjectChannels GEMM
       // whatever fuse_mod says, so ask about the launch that will actually run
-      const bool inj_emits = (fuse_mod && !use_cb) ? true : conv_gemm_emits_rowpart(u.dt, filled(g.inject, pi));
+      const bool inj_emits = (fuse_mod && !use_cb && !use_cbd) ? true : conv_gemm_emits_rowpart(u.dt, filled(g.inject, pi));
       fuse_attn = inj_emits && conv_gemm_ln_ok(u.dt, filled(g.qkv, pq));
     }
     if (use_cb) {
@@ -1111,6 +1122,63 @@ struct Exec {
       }
       if (g.attn) ai.pf = pf_for(g.qkv, (int)((l.rows + 31) / 32) * (C / 32), l.rows);
       else if (next && arm_gnpart(g.inject, ai, d)) gnpart_of = tB;   // tB becomes `cur` below
+      conv(g.inject, ai, u.dt, u.dt);
+    } else if (use_cbd) {
+      // Direct channel-block chain (conv_cb.hip, ConvCbArgs::epi) at C = 128: the first convolution stores h and the GroupNorm chunk statistics of
+      // h, the second applies GroupNorm+SiLU from them while staging its panel and finishes + x, LayerNorm, Modulation in its epilogue; the plain
+      // InjectChannels GEMM follows.  Every launch hosts the weight prefetch of the next one.
+      const int bt = p.Bt;
+      const double es = dsize(u.dt), rc = (double)l.rows * C;
+      const double cflops = 2.0 * rc * 3 * C, cbytes = 2.0 * rc * es + 3.0 * C * C * es;
+      const int mt = std::min(2, conv_cb_mt((int)l.rows, C, C));
+      const int cwgs = (int)((l.rows + 32 * mt - 1) / (32 * mt));
+      timed("gn_silu", 12.0 * rc, 3.0 * rc * es,
+            [&] { SF_HIP(launch_gn_silu(u.dt, cur, C, bt, l.L, C, G, g.gn1_g, g.gn1_b, 1e-5f, l.act, C, s, pf_cb(g.conv1, bt * G))); });
+      ConvCbArgs a;
+      a.src = l.act;
+      a.src_ld = C;
+      a.wp = g.conv1.wcb;
+      a.B = bt;
+      a.L = l.L;
+      a.C = a.N = C;
+      a.G = G;
+      a.eps = 1e-5f;
+      const CbGnPlan cgp = cb_gn_plan(l.L);   // the statistics chunks cb_reduce_gn would write
+      a.nch = cgp.nch;
+      a.chunk_rows = cgp.chunk_rows;
+      a.epi = 1;
+      a.out = tA;
+      a.out_ld = C;
+      a.bias = g.conv1.bias;
+      a.stats_out = p.slab;
+      a.pf = pf_cb(g.conv2, cwgs);
+      timed("conv_cb_gn", cflops + 6.0 * rc, cbytes, [&] { SF_HIP(launch_conv_cb(u.dt, a, s)); });
+      a.src = tA;
+      a.wp = g.conv2.wcb;
+      a.pro = 1;
+      a.stats = p.slab;
+      a.gamma = g.gn2_g;
+      a.beta = g.gn2_b;
+      a.epi = 2;
+      a.out = l.act;   // (the activated copy of x is dead: m takes its place, tB stays free for z)
+      a.bias = g.conv2.bias;
+      a.stats_out = nullptr;
+      a.res = cur;
+      a.res_ld = C;
+      a.ss = p.mod_all + g.mod_off;
+      a.ss_ld = p.mod_stride;
+      a.eps_ln = 1e-6f;
+      a.pf = pf_for(g.inject, cwgs, l.rows);
+      timed("conv_cb_ln", cflops + 24.0 * rc, cbytes + rc * es, [&] { SF_HIP(launch_conv_cb(u.dt, a, s)); });
+      stats_of = nullptr;
+      gnpart_of = nullptr;
+      ConvGemmArgs ai = inject_args(l.act, tB);   // InjectChannels on the modulated rows (+ collapsed cross-attention bias when no attention follows)
+      ai.short_k = 1;                             // K = 160: the 32x32 kernel the LayerNorm-folded form ran on, not the 64x64 tile
+      if (fuse_attn) {
+        ai.rowpart_out = rp_z;
+        ai.rowpart_nt = C / 32;
+      }
+      if (g.attn) ai.pf = pf_for(g.qkv, (int)((l.rows + 31) / 32) * (C / 32), l.rows);
       conv(g.inject, ai, u.dt, u.dt);
     } else {
     conv3(g.conv1, cur, tA, g.gn1_g, g.gn1_b, nullptr, nullptr);
