@@ -575,6 +575,66 @@ int sf_onset_detect(sf_audio_features *h, const float *wav, int B, int L, float 
                     int pre_avg, int post_avg, int wait, float delta, int conf_interval, int capacity, float *envelope, int32_t *count,
                     int32_t *positions, float *confidence, float *strength, void *ws, int64_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FAD evaluation (syncfusion_amd/fad.py)
+ *   replaces: main.evaluation.evaluate_fad (main/evaluation.py:7-28, the config.evaluation target of script/evaluate_diffusion.py:31-36):
+ *   frechet_audio_distance.FrechetAudioDistance(model_name="vggish", use_pca=False, use_activation=False) -- the VGGish input features
+ *   (vggish_input.py / mel_features.py), the torch.hub VGGish network and the embedding statistics.  The Frechet distance itself is
+ *   host arithmetic (fad.py).  All tensors fp32 unless stated, contiguous, on the device.
+ *
+ * sf_audio_features_create_framed   HOST-only, like sf_audio_features_create, for frames WITHOUT centring or clip padding: frame t covers
+ *     samples [t hop, t hop + win_length), is multiplied by a periodic Hann window of win_length points and zero-padded at its end to
+ *     n_fft points.  Same handle type, destroyed by sf_audio_features_destroy; sf_logmel_forward and sf_onset_detect refuse such a
+ *     handle (SF_ERR_INVALID) and sf_logmel_examples_forward refuses a centred one.  Refused: null pointers, n_fft not a power of two
+ *     in [256, 4096], win_length outside 1 .. n_fft, hop or n_mels < 1, a filter with an empty or out-of-range bin range, n_weights
+ *     that is not the sum of the bin counts (SF_ERR_INVALID).
+ * sf_logmel_examples_count     E = F / frames_per_example examples per clip of L samples, F = 1 + (L - win_length) / hop frames (0 for
+ *     L < win_length); the remainder of the frames is dropped.  -1 for a null or centred handle, L < 1 or frames_per_example < 1.
+ * sf_logmel_examples_forward   wav (B, L) -> examples: rows ((b E + e) frames_per_example + frame) n_mels + band of 4 columns, column 0 =
+ *     log(mel + log_offset) (natural log), columns 1 .. 3 = 0 -- the channels-last rows sf_vggish_forward reads -- and / or
+ *     mel (B, E frames_per_example, n_mels), the mel MAGNITUDE: filterbank times |X_k| (not power).  Either may be NULL (not both).
+ *     Refused before any HIP call: null pointers, B, L, frames_per_example < 1, log_offset <= 0 (SF_ERR_INVALID); E = 0, B > 65535,
+ *     an output of 2^31 bytes or more (SF_ERR_SHAPE).  No workspace.  A clip's rows do not depend on the rest of the batch.
+ *
+ * sf_vggish_create   stages[i] > 0: Conv2d(k = 3, pad = 1) to that many channels + bias + ReLU; stages[i] == 0: MaxPool2d(2, 2) (floor).
+ *     Input: one channel, H x W (96 frames x 64 bands).  Then n_fc Linear layers of fc_widths[i] outputs, ReLU after each but the last,
+ *     after the last only with final_relu (use_activation).  conv_w / conv_b / fc_w / fc_b: DEVICE pointers in layer order, PyTorch
+ *     layouts (cout, cin, 3, 3), (cout), (out, in), (out); the first Linear's columns run (h, w, c) over the last map, as torchvggish
+ *     flattens it.  Everything is packed into the engine's own memory before the call returns (on `stream`, synchronised): the
+ *     caller's tensors are not referenced afterwards.  Channel counts are padded to multiples of 8 columns (zeros) in the activations;
+ *     the packed weights hold zeros at those positions.  Refused before any HIP call: null pointers, counts outside 1 .. 64, channel
+ *     counts outside 0 .. 8192, no convolution, widths outside 1 .. 65536 (SF_ERR_INVALID); a pool of a map below 2 x 2 (SF_ERR_SHAPE);
+ *     a null weight or bias (SF_ERR_MISSING_WEIGHT).
+ * sf_vggish_max_examples / sf_vggish_workspace_bytes   the largest n of one call (every activation below 2^31 bytes) and the workspace
+ *     of n examples (monotone in n; -1 for a null handle or n outside 1 .. max).
+ * sf_vggish_forward  examples (n H W, 4) as written by sf_logmel_examples_forward -> embeddings (n, D) dense, D = fc_widths[n_fc - 1].
+ *     pool_taps: NULL, or one device pointer (or NULL) per max-pool that receives a copy of its output, rows (n, h, w) x padded
+ *     channels (tests).  Convolutions and Linears run on the implicit-GEMM launcher (fp32 MFMA, fp32 accumulation), Linears as 1x1
+ *     convolutions with one row per example.  Refused before any HIP call: null pointers, n < 1 (SF_ERR_INVALID), n above the maximum
+ *     (SF_ERR_SHAPE), a workspace below the query (SF_ERR_WORKSPACE).
+ * sf_op_maxpool2x2_cl   the engine's pool alone: x rows (n, H, W) x ld -> y rows (n, H / 2, W / 2) x ld, every column alike (padding
+ *     columns stay zero), the last row / column of an odd extent dropped.  Refused: null pointers, n, ld < 1, H, W < 2 (SF_ERR_INVALID).
+ * sf_op_moments   x (n, D), D <= 128 -> sum (D) and scatter (D, D) in fp64: sum[d] = sum_r x[r][d], scatter[i][j] = sum_r (x[r][i] -
+ *     sum[i] / n)(x[r][j] - sum[j] / n) (two passes about the mean).  np.cov(x, rowvar=False) = scatter / (n - 1).  Fixed summation order,
+ *     no atomics: identical input gives identical bits; scatter is exactly symmetric.  Refused: null pointers, n < 1 (SF_ERR_INVALID),
+ *     D outside 1 .. 128 (SF_ERR_SHAPE). */
+typedef struct sf_vggish sf_vggish;
+int sf_audio_features_create_framed(int n_fft, int win_length, int hop, int n_mels, const int32_t *first_bin /*host*/,
+                                    const int32_t *bin_count /*host*/, const float *weights /*host*/, int64_t n_weights, sf_audio_features **out);
+int sf_logmel_examples_count(const sf_audio_features *h, int L, int frames_per_example);
+int sf_logmel_examples_forward(sf_audio_features *h, const float *wav, int B, int L, int frames_per_example, float log_offset, float *examples,
+                               float *mel, void *stream);
+int sf_vggish_create(int n_stages, const int32_t *stages /*host*/, int n_fc, const int32_t *fc_widths /*host*/, int H, int W, int final_relu,
+                     const void *const *conv_w, const void *const *conv_b, const void *const *fc_w, const void *const *fc_b, void *stream,
+                     sf_vggish **out);
+void sf_vggish_destroy(sf_vggish *h);
+int sf_vggish_max_examples(const sf_vggish *h);
+int64_t sf_vggish_workspace_bytes(const sf_vggish *h, int n);
+int sf_vggish_forward(sf_vggish *h, const float *examples, int n, float *embeddings, float *const *pool_taps, void *ws, int64_t ws_bytes,
+                      void *stream);
+int sf_op_maxpool2x2_cl(const float *x, int64_t n, int H, int W, int ld, float *y, void *stream);
+int sf_op_moments(const float *x, int64_t n, int D, double *sum, double *scatter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

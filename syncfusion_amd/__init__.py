@@ -6,12 +6,13 @@ Public surface = the reference's own: ``DiffusionModel`` 
 runs in ``lib/libsyncfusion_amd.so`` (hand-written HIP, C ABI in include/syncfusion_amd.h).
 """
 from . import _lib  # noqa: F401
-from . import audio_features, autograd, evaluation, frame_transforms, onset_training, shards, training, video_chunks  # noqa: F401
+from . import audio_features, autograd, evaluation, fad, frame_transforms, onset_training, shards, training, video_chunks  # noqa: F401
 from .config import instantiate, instantiate_class, instantiate_frames_transforms, instantiate_model_yaml
 from .diffusion import DiffusionModel, LinearSchedule, UNetV0, VDiffusion, VSampler
 from .audio_features import MelSpectrogram, mel_filterbank, onset_detect, onset_strength
 from .encoder1d import Encoder1d
 from .evaluation import evaluate_onsets
+from .fad import VGGish, VGGishConfig, embedding_statistics, evaluate_fad, frechet_distance
 from .generation import generate_batch, generate_dataset
 from .module import Model, RandomEmbedder
 from .module_onset import Model as OnsetModel
@@ -24,5 +25,6 @@ from .training import allreduce_gradients
 __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule", "Encoder1d", "VideoOnsetNet", "Model", "OnsetModel",
            "GraphedOnsetTrainStep",           "RandomEmbedder", "generate_batch", "generate_dataset", "instantiate", "instantiate_model_yaml", "onsets_to_track", "cut_prefix_crop", "resample",
            "allreduce_gradients", "frame_transforms", "instantiate_class", "instantiate_frames_transforms",
-           "audio_features", "evaluation", "MelSpectrogram", "mel_filterbank", "onset_detect", "onset_strength", "evaluate_onsets"]
+           "audio_features", "evaluation", "MelSpectrogram", "mel_filterbank", "onset_detect", "onset_strength", "evaluate_onsets",
+           "fad", "VGGish", "VGGishConfig", "embedding_statistics", "frechet_distance", "evaluate_fad"]
 __version__ = "0.1.0"

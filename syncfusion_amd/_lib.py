@@ -189,6 +189,21 @@ SYMBOLS = {
     # (h, wav, B, L, amin, top_db, lag, pre_max, post_max, pre_avg, post_avg, wait, delta, conf_interval, capacity, envelope, count, positions,
     #  confidence, strength, ws, ws_bytes, stream)
     "sf_onset_detect": (_I, [_P, _P, _I, _I, _F, _F, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
+    # the FAD evaluation (syncfusion_amd/fad.py)
+    # (n_fft, win_length, hop, n_mels, first_bin_host, bin_count_host, weights_host, n_weights, out)
+    "sf_audio_features_create_framed": (_I, [_I, _I, _I, _I, _P, _P, _P, _L, C.POINTER(_P)]),
+    "sf_logmel_examples_count": (_I, [_P, _I, _I]),
+    # (h, wav, B, L, frames_per_example, log_offset, examples, mel, stream)
+    "sf_logmel_examples_forward": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    # (n_stages, stages_host, n_fc, fc_widths_host, H, W, final_relu, conv_w, conv_b, fc_w, fc_b, stream, out)
+    "sf_vggish_create": (_I, [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, C.POINTER(_P)]),
+    "sf_vggish_destroy": (None, [_P]),
+    "sf_vggish_max_examples": (_I, [_P]),
+    "sf_vggish_workspace_bytes": (_L, [_P, _I]),
+    # (h, examples, n, embeddings, pool_taps, ws, ws_bytes, stream)
+    "sf_vggish_forward": (_I, [_P, _P, _I, _P, _P, _P, _L, _P]),
+    "sf_op_maxpool2x2_cl": (_I, [_P, _L, _I, _I, _I, _P, _P]),
+    "sf_op_moments": (_I, [_P, _L, _I, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -7,7 +7,7 @@
 
 namespace sf {
 
-enum { AUDIO_PAD_CONSTANT = 0, AUDIO_PAD_REFLECT = 1 };
+enum { AUDIO_PAD_CONSTANT = 0, AUDIO_PAD_REFLECT = 1, AUDIO_PAD_NONE = 2 /* uncentred frames: launch_framed_logmel only */ };
 
 // Device tables of one front-end configuration (owned by the handle in capi_audio.cpp).
 struct AudioTables {
@@ -34,6 +34,10 @@ int64_t audio_ws_bytes(int n_mels, int hop, int B, int L);
 
 // wav (B, L) -> mel power (B, n_mels, T): one workgroup per (clip, frame), real FFT in LDS
 hipError_t launch_mel_power(const AudioTables &tab, const float *wav, int B, int L, float *mel, hipStream_t s);
+// uncentred frames of `win` samples (the table's window holds zeros from `win` on) -> log(mel magnitude + log_offset) as 4-column example
+// rows ((b T + t) n_mels + m) and / or the (B, T, n_mels) magnitude plane (either may be null); T frames per clip, all inside the clip
+hipError_t launch_framed_logmel(const AudioTables &tab, int win, const float *wav, int B, int L, int T, float log_offset, float *examples,
+                                float *mel, hipStream_t s);
 // mel power -> dB plane (optional) and onset envelope (optional): one workgroup per clip
 hipError_t launch_db_flux(const float *mel, int B, int n_mels, int T, float amin, float amin_db, float top_db, int lag, int shift, float *db,
                           float *env, hipStream_t s);

@@ -32,6 +32,52 @@ template <bool IS_MAX> __device__ __forceinline__ float block_reduce(float v, fl
   return red[0];
 }
 
+// ---- real FFT of the packed frame in LDS ------------------------------------------------------------------------------------------------------
+// lds: 4 arrays of M = n_fft / 2 floats.  On entry the first two hold z[n] = x[2n] + i x[2n + 1] (already windowed) and the block is
+// synchronised; on return the pointer given back holds bins 0 .. M of the real transform, |X_k|^2 (MAGNITUDE = false) or |X_k| (true),
+// and the block is synchronised again.  Shared by the centred power front end and the uncentred magnitude one: one FFT in the library.
+template <bool MAGNITUDE> __device__ __forceinline__ const float *real_fft_bins(const AudioTables &tab, float *lds, int tid) {
+  const int N = tab.n_fft, M = N >> 1;
+  float *sr = lds, *si = lds + M, *dr = lds + 2 * M, *di = lds + 3 * M;   // source / destination images, swapped after every stage
+  // Stockham radix-2, M points, log2(M) stages
+  const int half = M >> 1;
+  for (int Ns = 1; Ns < M; Ns <<= 1) {
+    const int tw_step = M / Ns;        // exp(-2 pi i k / (2 Ns)) = table[k * M / Ns] of the n_fft-point table
+    for (int j = tid; j < half; j += AF_THREADS) {
+      const int k = j & (Ns - 1);
+      const float wr = tab.tw_re[k * tw_step], wi = tab.tw_im[k * tw_step];
+      const float ar = sr[j], ai = si[j];
+      const float br = sr[j + half], bi = si[j + half];
+      const float cr = br * wr - bi * wi, ci = br * wi + bi * wr;
+      const int j0 = ((j - k) << 1) + k;
+      dr[j0] = ar + cr;
+      di[j0] = ai + ci;
+      dr[j0 + Ns] = ar - cr;
+      di[j0 + Ns] = ai - ci;
+    }
+    float *tr = sr, *ti = si;
+    sr = dr, si = di, dr = tr, di = ti;
+    __syncthreads();
+  }
+
+  // unpack to the real transform's bins 0 .. M; power or magnitude
+  const float *zr = sr, *zi = si;
+  float *pw = dr;                      // M + 1 floats fit the 2 M of the other image (its re and im arrays are adjacent)
+  for (int k = tid; k <= M; k += AF_THREADS) {
+    const int k0 = k & (M - 1), k1 = (M - k) & (M - 1);
+    const float a = zr[k0], bb = zi[k0], c = zr[k1], d = zi[k1];
+    const float er = 0.5f * (a + c), ei = 0.5f * (bb - d);
+    const float orr = 0.5f * (bb + d), oi = -0.5f * (a - c);
+    const float wr = tab.tw_re[k], wi = tab.tw_im[k];
+    const float xr = er + (wr * orr - wi * oi);
+    const float xi = ei + (wr * oi + wi * orr);
+    const float p2 = xr * xr + xi * xi;
+    pw[k] = MAGNITUDE ? sqrtf(p2) : p2;
+  }
+  __syncthreads();
+  return pw;
+}
+
 // ---- framed power spectrum -> mel power -----------------------------------------------------------------------------------------------------
 // dynamic LDS: 4 arrays of M = n_fft / 2 floats (re / im of two images) = 8 * n_fft bytes.
 __global__ __launch_bounds__(AF_THREADS) void mel_power_kernel(AudioTables tab, const float *__restrict__ wav, int L, int T,
@@ -39,7 +85,7 @@ __global__ __launch_bounds__(AF_THREADS) void mel_power_kernel(AudioTables tab, 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int N = tab.n_fft, M = N >> 1;
   const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  float *sr = lds, *si = lds + M, *dr = lds + 2 * M, *di = lds + 3 * M;   // source / destination images, swapped after every stage
+  float *sr = lds, *si = lds + M;
   const float *x = wav + (size_t)b * L;
   const int start = t * tab.hop - M;
 
@@ -65,41 +111,7 @@ __global__ __launch_bounds__(AF_THREADS) void mel_power_kernel(AudioTables tab, 
   }
   __syncthreads();
 
-  // Stockham radix-2, M points, log2(M) stages
-  const int half = M >> 1;
-  for (int Ns = 1; Ns < M; Ns <<= 1) {
-    const int tw_step = M / Ns;        // exp(-2 pi i k / (2 Ns)) = table[k * M / Ns] of the n_fft-point table
-    for (int j = tid; j < half; j += AF_THREADS) {
-      const int k = j & (Ns - 1);
-      const float wr = tab.tw_re[k * tw_step], wi = tab.tw_im[k * tw_step];
-      const float ar = sr[j], ai = si[j];
-      const float br = sr[j + half], bi = si[j + half];
-      const float cr = br * wr - bi * wi, ci = br * wi + bi * wr;
-      const int j0 = ((j - k) << 1) + k;
-      dr[j0] = ar + cr;
-      di[j0] = ai + ci;
-      dr[j0 + Ns] = ar - cr;
-      di[j0 + Ns] = ai - ci;
-    }
-    float *tr = sr, *ti = si;
-    sr = dr, si = di, dr = tr, di = ti;
-    __syncthreads();
-  }
-
-  // unpack to the real transform's bins 0 .. M and square
-  const float *zr = sr, *zi = si;
-  float *pw = dr;                      // M + 1 floats fit the 2 M of the other image (its re and im arrays are adjacent)
-  for (int k = tid; k <= M; k += AF_THREADS) {
-    const int k0 = k & (M - 1), k1 = (M - k) & (M - 1);
-    const float a = zr[k0], bb = zi[k0], c = zr[k1], d = zi[k1];
-    const float er = 0.5f * (a + c), ei = 0.5f * (bb - d);
-    const float orr = 0.5f * (bb + d), oi = -0.5f * (a - c);
-    const float wr = tab.tw_re[k], wi = tab.tw_im[k];
-    const float xr = er + (wr * orr - wi * oi);
-    const float xi = ei + (wr * oi + wi * orr);
-    pw[k] = xr * xr + xi * xi;
-  }
-  __syncthreads();
+  const float *pw = real_fft_bins<false>(tab, lds, tid);
 
   for (int m = tid; m < tab.n_mels; m += AF_THREADS) {
     const int first = tab.fb_first[m], cnt = tab.fb_count[m];
@@ -107,6 +119,39 @@ __global__ __launch_bounds__(AF_THREADS) void mel_power_kernel(AudioTables tab, 
     float acc = 0.f;
     for (int i = 0; i < cnt; ++i) acc += w[i] * pw[first + i];
     mel[((size_t)b * tab.n_mels + m) * T + t] = acc;
+  }
+}
+
+// ---- uncentred frames -> log-mel magnitude examples (the VGGish input of the FAD evaluation) ------------------------------------------------
+// One workgroup per (clip, frame): frame t = samples [t hop, t hop + win) times the window, zero-padded at its END to n_fft points, no
+// padding of the clip (the caller launches only frames that lie inside it); |X_k|, filterbank, log(mel + offset).  The frame's n_mels
+// values go to rows ((b T + t) n_mels + m) of a 4-column channels-last image (column 0 the value, columns 1 .. 3 zero: the layout the
+// implicit-GEMM convolution reads with cin_ld = 4) and / or to a plain (B, T, n_mels) magnitude plane.
+__global__ __launch_bounds__(AF_THREADS) void framed_logmel_kernel(AudioTables tab, int win, const float *__restrict__ wav, int L, int T,
+                                                                   float log_offset, float4 *__restrict__ examples, float *__restrict__ mel) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int M = tab.n_fft >> 1;
+  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  float *sr = lds, *si = lds + M;
+  const float *x = wav + (size_t)b * L + (size_t)t * tab.hop;   // t hop + win <= L for every launched frame
+
+  for (int n = tid; n < M; n += AF_THREADS) {
+    const int i = 2 * n;
+    sr[n] = i < win ? x[i] * tab.window[i] : 0.f;
+    si[n] = i + 1 < win ? x[i + 1] * tab.window[i + 1] : 0.f;
+  }
+  __syncthreads();
+
+  const float *mag = real_fft_bins<true>(tab, lds, tid);
+
+  for (int m = tid; m < tab.n_mels; m += AF_THREADS) {
+    const int first = tab.fb_first[m], cnt = tab.fb_count[m];
+    const float *w = tab.fb_weights + tab.fb_offset[m];
+    float acc = 0.f;
+    for (int i = 0; i < cnt; ++i) acc += w[i] * mag[first + i];
+    const size_t row = ((size_t)b * T + t) * tab.n_mels + m;
+    if (mel) mel[row] = acc;
+    if (examples) examples[row] = make_float4(logf(acc + log_offset), 0.f, 0.f, 0.f);
   }
 }
 
@@ -256,6 +301,14 @@ hipError_t launch_mel_power(const AudioTables &tab, const float *wav, int B, int
   const int T = audio_frames(L, tab.hop);
   if (B > 65535) return hipErrorInvalidValue;
   hipLaunchKernelGGL(mel_power_kernel, dim3(T, B), dim3(AF_THREADS), (size_t)8 * tab.n_fft, s, tab, wav, L, T, mel);
+  return hipGetLastError();
+}
+
+hipError_t launch_framed_logmel(const AudioTables &tab, int win, const float *wav, int B, int L, int T, float log_offset, float *examples,
+                                float *mel, hipStream_t s) {
+  if (B > 65535 || T < 1 || (int64_t)(T - 1) * tab.hop + win > L) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(framed_logmel_kernel, dim3(T, B), dim3(AF_THREADS), (size_t)8 * tab.n_fft, s, tab, win, wav, L, T, log_offset,
+                     reinterpret_cast<float4 *>(examples), mel);
   return hipGetLastError();
 }
 

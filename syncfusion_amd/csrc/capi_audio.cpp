@@ -1,5 +1,6 @@
 // C ABI of the audio front end (audio_features.hip): the handle with the window, twiddle and filterbank tables, the workspace query,
-// sf_logmel_forward and sf_onset_detect.  Arguments are checked before the first HIP call, so every refusal is reported without a device.
+// sf_logmel_forward, sf_onset_detect and the uncentred pair sf_audio_features_create_framed / sf_logmel_examples_forward.  Arguments are
+// checked before the first HIP call, so every refusal is reported without a device.
 #include <cmath>
 #include <cstring>
 #include <exception>
@@ -23,6 +24,7 @@ using namespace sf;
 
 struct sf_audio_features {
   AudioTables tab;                    // device pointers into `dev` once uploaded
+  int win = 0;                        // uncentred handles (sf_audio_features_create_framed): window length <= n_fft
   std::vector<float> h_window, h_tw_re, h_tw_im, h_weights;
   std::vector<int32_t> h_first, h_count, h_offset;
   void *dev = nullptr;
@@ -70,6 +72,7 @@ static int check_call(const sf_audio_features *h, const float *wav, int B, int L
   if (!h || !wav) fail(SF_ERR_INVALID, "null argument");
   if (B < 1 || L < 1) fail(SF_ERR_INVALID, "B and L must be at least 1");
   if (B > 65535) fail(SF_ERR_SHAPE, "at most 65535 clips per call");
+  if (h->tab.pad_mode == AUDIO_PAD_NONE) fail(SF_ERR_INVALID, "the handle frames without centring: sf_logmel_examples_forward is its only forward call");
   if (h->tab.pad_mode == AUDIO_PAD_REFLECT && L <= h->tab.n_fft / 2) fail(SF_ERR_SHAPE, "reflect padding needs L > n_fft / 2 (L = %d, n_fft = %d)", L, h->tab.n_fft);
   const int64_t T = audio_frames(L, h->tab.hop);
   if ((int64_t)B * h->tab.n_mels * T >= (1ll << 31) || (int64_t)B * L >= (1ll << 40)) fail(SF_ERR_SHAPE, "batch too large");
@@ -78,17 +81,13 @@ static int check_call(const sf_audio_features *h, const float *wav, int B, int L
   return (int)T;
 }
 
-extern "C" {
-
-int sf_audio_features_create(int n_fft, int hop, int n_mels, int pad_mode, const int32_t *first_bin, const int32_t *bin_count,
-                             const float *weights, int64_t n_weights, sf_audio_features **out) {
-  SF_API_BEGIN
-  if (!out || !first_bin || !bin_count || !weights) fail(SF_ERR_INVALID, "null argument");
-  *out = nullptr;
+// checks and host tables shared by the two create calls; window: periodic Hann of `win` points, zeros up to n_fft
+static sf_audio_features *create_handle(int n_fft, int win, int hop, int n_mels, int pad_mode, const int32_t *first_bin, const int32_t *bin_count,
+                                        const float *weights, int64_t n_weights) {
   if (n_fft < 256 || n_fft > 4096 || (n_fft & (n_fft - 1))) fail(SF_ERR_INVALID, "n_fft must be a power of two in [256, 4096], got %d", n_fft);
+  if (win < 1 || win > n_fft) fail(SF_ERR_INVALID, "the window must have 1 .. n_fft = %d points, got %d", n_fft, win);
   if (hop < 1) fail(SF_ERR_INVALID, "hop must be at least 1");
   if (n_mels < 1) fail(SF_ERR_INVALID, "n_mels must be at least 1");
-  if (pad_mode != AUDIO_PAD_CONSTANT && pad_mode != AUDIO_PAD_REFLECT) fail(SF_ERR_INVALID, "pad_mode must be 0 (constant) or 1 (reflect)");
   const int bins = n_fft / 2 + 1;
   int64_t total = 0;
   std::vector<int32_t> offset(n_mels);
@@ -101,8 +100,9 @@ int sf_audio_features_create(int n_fft, int hop, int n_mels, int pad_mode, const
   if (total != n_weights) fail(SF_ERR_INVALID, "%lld packed weights given, the bin counts add up to %lld", (long long)n_weights, (long long)total);
   auto *h = new sf_audio_features();
   h->tab.n_fft = n_fft, h->tab.hop = hop, h->tab.n_mels = n_mels, h->tab.pad_mode = pad_mode;
-  h->h_window.resize(n_fft);
-  for (int i = 0; i < n_fft; ++i) h->h_window[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / n_fft));   // periodic Hann
+  h->win = win;
+  h->h_window.assign(n_fft, 0.f);
+  for (int i = 0; i < win; ++i) h->h_window[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / win));   // periodic Hann
   h->h_tw_re.resize(bins), h->h_tw_im.resize(bins);
   for (int k = 0; k < bins; ++k) {
     h->h_tw_re[k] = (float)std::cos(2.0 * M_PI * k / n_fft);
@@ -112,7 +112,28 @@ int sf_audio_features_create(int n_fft, int hop, int n_mels, int pad_mode, const
   h->h_count.assign(bin_count, bin_count + n_mels);
   h->h_offset = offset;
   h->h_weights.assign(weights, weights + n_weights);
-  *out = h;
+  return h;
+}
+
+extern "C" {
+
+int sf_audio_features_create(int n_fft, int hop, int n_mels, int pad_mode, const int32_t *first_bin, const int32_t *bin_count,
+                             const float *weights, int64_t n_weights, sf_audio_features **out) {
+  SF_API_BEGIN
+  if (!out || !first_bin || !bin_count || !weights) fail(SF_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (pad_mode != AUDIO_PAD_CONSTANT && pad_mode != AUDIO_PAD_REFLECT) fail(SF_ERR_INVALID, "pad_mode must be 0 (constant) or 1 (reflect)");
+  *out = create_handle(n_fft, n_fft, hop, n_mels, pad_mode, first_bin, bin_count, weights, n_weights);
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_audio_features_create_framed(int n_fft, int win_length, int hop, int n_mels, const int32_t *first_bin, const int32_t *bin_count,
+                                    const float *weights, int64_t n_weights, sf_audio_features **out) {
+  SF_API_BEGIN
+  if (!out || !first_bin || !bin_count || !weights) fail(SF_ERR_INVALID, "null argument");
+  *out = nullptr;
+  *out = create_handle(n_fft, win_length, hop, n_mels, AUDIO_PAD_NONE, first_bin, bin_count, weights, n_weights);
   return SF_OK;
   SF_API_END
 }
@@ -162,6 +183,31 @@ int sf_onset_detect(sf_audio_features *h, const float *wav, int B, int L, float 
   SF_HIP(launch_mel_power(h->tab, wav, B, L, mel, s));
   SF_HIP(launch_db_flux(mel, B, h->tab.n_mels, T, amin, (float)(10.0 * std::log10((double)amin)), top_db, lag, p.shift, nullptr, envelope, s));
   SF_HIP(launch_peak_pick(envelope, wav, B, T, L, h->tab.hop, p, x, flags, count, positions, confidence, strength, s));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_logmel_examples_count(const sf_audio_features *h, int L, int frames_per_example) {
+  if (!h || h->tab.pad_mode != AUDIO_PAD_NONE || L < 1 || frames_per_example < 1) return -1;
+  const int64_t F = L < h->win ? 0 : 1 + (int64_t)(L - h->win) / h->tab.hop;
+  return (int)(F / frames_per_example);
+}
+
+int sf_logmel_examples_forward(sf_audio_features *h, const float *wav, int B, int L, int frames_per_example, float log_offset, float *examples,
+                               float *mel, void *stream) {
+  SF_API_BEGIN
+  if (!h || !wav) fail(SF_ERR_INVALID, "null argument");
+  if (!examples && !mel) fail(SF_ERR_INVALID, "null argument: neither examples nor mel asked for");
+  if (h->tab.pad_mode != AUDIO_PAD_NONE) fail(SF_ERR_INVALID, "the handle was not made by sf_audio_features_create_framed");
+  if (B < 1 || L < 1 || frames_per_example < 1) fail(SF_ERR_INVALID, "B, L and frames_per_example must be at least 1");
+  if (!(log_offset > 0.f)) fail(SF_ERR_INVALID, "log_offset must be positive");
+  if (B > 65535) fail(SF_ERR_SHAPE, "at most 65535 clips per call");
+  const int E = sf_logmel_examples_count(h, L, frames_per_example);
+  if (E < 1) fail(SF_ERR_SHAPE, "a clip of %d samples holds no example of %d frames (window %d, hop %d)", L, frames_per_example, h->win, h->tab.hop);
+  const int64_t T = (int64_t)E * frames_per_example;
+  if ((int64_t)B * T * h->tab.n_mels * 4 >= (1ll << 31) || T > 65535 * 16) fail(SF_ERR_SHAPE, "batch too large");
+  upload(h);
+  SF_HIP(launch_framed_logmel(h->tab, h->win, wav, B, L, (int)T, log_offset, examples, mel, static_cast<hipStream_t>(stream)));
   return SF_OK;
   SF_API_END
 }
