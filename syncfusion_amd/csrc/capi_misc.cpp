@@ -262,8 +262,8 @@ static int conv1d_cl_impl(int dtype, const void *x, const float *w, const float 
   bool want_rs = false;
   if (wx_ok && groups == 0 && (K % 64) == 0 && K <= 1280 && (N % 32) == 0 && (C % 16) == 0) {
     ConvGemmArgs pa = a;
-    pa.w = pa.wx = pa.wfrx = reinterpret_cast<const void *>(16);   // probe
-    want_rs = strncmp(conv_gemm_variant_name(dtype, pa), "conv_gemm_rs", 12) == 0;
+    pa.w = pa.wx = pa.wfrx = &pa;   // every image exists (only whether one does enters the plan)
+    want_rs = conv_gemm_plan(dtype, pa).family == CG_RS;
   }
   void *wx_done = nullptr;
   // which images the training step reads of this weight: the fp32 [N][K] matrix only where the chosen kernel is not a split-operand one
@@ -318,13 +318,14 @@ static int conv1d_cl_impl(int dtype, const void *x, const float *w, const float 
     if (!label_out) SF_HIP(launch_pack_wfrx(static_cast<const float *>(wp), N, K, wfrx, s));
     a.wfrx = wfrx;
   }
+  const ConvGemmPlan pl = direct ? ConvGemmPlan() : conv_gemm_plan(dtype, a);
   if (label_out) {   // the ConvGemmArgs are finished: name the launch below instead of making it
     if (!direct && !conv_gemm_supported(dtype, a)) fail(SF_ERR_UNSUPPORTED, "no GEMM kernel takes this shape");
-    *label_out = direct ? "conv_direct" : conv_gemm_variant_name(dtype, a);
+    *label_out = direct ? "conv_direct" : pl.label;
     return SF_OK;
   }
   if (direct) SF_HIP(launch_conv_direct(dtype, dtype, a, s));
-  else SF_HIP(launch_conv_gemm(dtype, a, s));
+  else SF_HIP(launch_conv_gemm_planned(dtype, a, pl, s));
   return SF_OK;
   SF_API_END
 }

@@ -108,17 +108,18 @@ static int conv1d_bwd_impl(int dtype, const float *x, const float *act_saved, co
     if (dg.refused) fail(SF_ERR_UNSUPPORTED, "dgrad of a thin convolution (N %% 32 != 0) needs C <= 32 and its weight matrix within conv_direct's 64 KiB of LDS");
     const bool direct = dg.direct, wx_dg = dg.split;
     ConvGemmArgs &a = dg.a;
-    if (dgrad_pack) {   // images written by sf_op_conv1d_train_fwd: the fp32 matrix only if this launch reads it (the same predicate there)
+    if (dgrad_pack) {   // images written by sf_op_conv1d_train_fwd
       p.wd = const_cast<float *>(static_cast<const float *>(dgrad_pack));
       p.wdx = p.wd + (int64_t)C * taps * p.ldn;
-      if (wx_dg && conv_gemm_reads_split_only(F32, a)) p.wd = nullptr;
     } else {
       SF_HIP(launch_pack_dgrad(w, N, C, taps, p.ldn, p.wd, s, wx_dg ? p.wdx : nullptr));
     }
-    a.w = p.wd;
     if (wx_dg) a.wx = p.wdx;   // products from split bf16 operands
+    const ConvGemmPlan pl = conv_gemm_plan(F32, a);   // decided once: which images the launch reads, and the launch
+    if (dgrad_pack && pl.split) p.wd = nullptr;       // the fp32 matrix was written only if this launch reads it (the same predicate there)
+    a.w = p.wd;
     if (direct) SF_HIP(launch_conv_direct(F32, F32, a, s));
-    else SF_HIP(launch_conv_gemm(F32, a, s));
+    else SF_HIP(launch_conv_gemm_planned(F32, a, pl, s));
   }
   // ---- wgrad / bias grad ------------------------------------------------------------------------------------------
   // (the bias gradient's slice sums first: their reduction rides on the weight gradient's reducer launch where there is one)
@@ -176,7 +177,7 @@ int sf_op_conv1d_bwd_variant(int dtype, int B, int L, int C, int N, int taps, in
     dg.a.w = reinterpret_cast<const void *>(16);
     if (dg.split) dg.a.wx = reinterpret_cast<const void *>(16);
     if (!dg.direct && !conv_gemm_supported(F32, dg.a)) fail(SF_ERR_UNSUPPORTED, "no GEMM kernel takes this data gradient");
-    dname = dg.direct ? "conv_direct" : conv_gemm_variant_name(F32, dg.a);
+    dname = dg.direct ? "conv_direct" : conv_gemm_plan(F32, dg.a).label;
   }
   // wgrad / bias grad: the same plan functions the launchers switch on
   const ConvWgradPlan wp = conv_wgrad_plan(rows, C, N, taps, conv_wgrad_splits(rows, C, N, taps), x3 ? X3_BF16 : 0);

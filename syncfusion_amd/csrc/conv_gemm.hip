@@ -363,8 +363,64 @@ hipError_t launch_cfg(const ConvGemmArgs &a, hipStream_t s) {
 }
 
 // tile variants: 0 scalar-A 64x64, 1 128x32, 2 128x64, 3 64x64, 4 128x128
-int pick_variant(const ConvGemmArgs &a);
-int pick_variant(const ConvGemmArgs &a) {
+template <typename T> hipError_t launch_classic(const ConvGemmArgs &a, int tile, hipStream_t s) {
+  switch (tile) {
+    case 0: return launch_cfg<T, 64, 64, 2, 2, true>(a, s);
+    case 1: return launch_cfg<T, 128, 32, 4, 1, false>(a, s);
+    case 2: return launch_cfg<T, 128, 64, 2, 2, false>(a, s);
+    case 3: return launch_cfg<T, 64, 64, 2, 2, false>(a, s);
+    case 4: return launch_cfg<T, 128, 128, 2, 2, false>(a, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// One name table per family: labels are profiling keys and test keys, built once from (family, tile, operand type) and kept by pointer.
+struct Labels {
+  static constexpr int NT = CG_MT_TILES;
+  const char *at[CG_MT + 1][NT + 1][4] = {};   // [family][tile; NT = no tile in the name][f32, x3, bf16, f16]
+  std::set<std::string> pool;
+  Labels() {
+    static const char *const stem[CG_MT + 1] = {nullptr, "conv_gemm", "conv_gemm_v2", "conv_gemm_sk", "conv_gemm_fast", "conv_gemm_wp", "conv_gemm_rs", "conv_gemm_mt"};
+    static const char *const tiles[CG_MT + 1][NT] = {
+        {},
+        {"64x64,scalarA", "128x32", "128x64", "64x64", "128x128"},
+        {"128x128", "128x64", "64x64"},
+        {"64x64", "64x32", "32x32"},
+        {"64x64", "64x32", "32x32"},
+        {"64x64", "64x32", "32x32"},
+        {"32x32"},
+        {"256x128", "128x128", "128x192", "192x128", "256x64", "128x128,2wg", "128x192,2wg", "128x64,2wg", "192x128,2wg", "256x64,2wg", "256x256"}};
+    static const char *const type[3] = {"f32", "x3", "bf16"};
+    for (int f = CG_CLASSIC; f <= CG_MT; ++f)
+      for (int t = 0; t <= NT; ++t)
+        for (int ty = 0; ty < 3; ++ty) {
+          if (t < NT && !tiles[f][t]) continue;
+          const std::string name = std::string(stem[f]) + "<" + type[ty] + (t < NT ? std::string(",") + tiles[f][t] : std::string()) + ">";
+          at[f][t][ty] = pool.insert(name).first->c_str();
+          if (ty == 2) at[f][t][3] = label_for_dtype(F16, at[f][t][2]);
+        }
+  }
+};
+const char *plan_label(int dt, const ConvGemmPlan &p) {
+  static const Labels l;
+  if (p.family == CG_INVALID) return "conv_gemm<invalid>";
+  const bool no_tile = p.family == CG_MT && dt == F32;   // conv_gemm_mt<f32> / conv_gemm_mt<x3>: one label for every tile
+  const char *name = l.at[p.family][no_tile ? Labels::NT : p.tile][dt == F32 ? (p.split ? 1 : 0) : dt == BF16 ? 2 : 3];
+  return name ? name : "conv_gemm<invalid>";
+}
+
+// tuning hook: below this many 64x64 tiles a GEMM goes to the wave-split-K / wave-private kernels
+long short_act_tiles() {
+  static const long v = [] {
+    const char *e = tune_env("SF_SHORT_TILES");
+    const long t = e ? atol(e) : 0;
+    return t > 0 ? t : 500L;
+  }();
+  return v;
+}
+
+// classic tile: 0 scalar-A 64x64, 1 128x32, 2 128x64, 3 64x64, 4 128x128; -1: no classic kernel takes the shape
+int classic_tile(const ConvGemmArgs &a) {
   if (g_conv_gemm_force.path == 1 && g_conv_gemm_force.tile >= 1 && g_conv_gemm_force.tile <= 4) return g_conv_gemm_force.tile;
   const bool scalar_a = (a.cin % BK) != 0 || (a.cin2 % BK) != 0;
   if (scalar_a) return (a.cin2 != 0 || a.pro != 0) ? -1 : 0;
@@ -377,18 +433,26 @@ int pick_variant(const ConvGemmArgs &a) {
   return 3;
 }
 
-template <typename T> hipError_t dispatch(const ConvGemmArgs &a, hipStream_t s) {
-  switch (pick_variant(a)) {
-    case 0: return launch_cfg<T, 64, 64, 2, 2, true>(a, s);
-    case 1: return launch_cfg<T, 128, 32, 4, 1, false>(a, s);
-    case 2: return launch_cfg<T, 128, 64, 2, 2, false>(a, s);
-    case 3: return launch_cfg<T, 64, 64, 2, 2, false>(a, s);
-    case 4: return launch_cfg<T, 128, 128, 2, 2, false>(a, s);
-    default: return hipErrorInvalidValue;
-  }
+bool mt_wanted(int dt, const ConvGemmArgs &a) { return conv_gemm_mt_ok(dt, a) && conv_gemm_mt_prefers(dt, a); }
+
+ConvGemmPlan mt_plan(int dt, const ConvGemmArgs &a) {
+  ConvGemmPlan p;
+  p.family = CG_MT;
+  p.tile = conv_gemm_mt_tile(dt, a);
+  p.split = dt == F32 && a.wx ? (a.wx_mode == X3_BF16 ? X3_BF16 : X3_F16) : 0;
+  return p;
 }
 
+ConvGemmArgs without_rowpart(ConvGemmArgs a) {
+  a.rowpart_out = nullptr;
+  return a;
+}
+
+alignas(16) float g_armed[4];   // what a query arms its copy of the arguments with: only whether a pointer is set enters a plan
+
 }  // namespace
+
+ConvGemmForce g_conv_gemm_force;
 
 bool conv_gemm_supported(int dt, const ConvGemmArgs &a) {
   (void)dt;
@@ -401,21 +465,6 @@ bool conv_gemm_supported(int dt, const ConvGemmArgs &a) {
   return true;
 }
 
-// short activations (the classic tiling would leave most CUs idle) go to the wave-split-K kernel
-hipError_t launch_conv_gemm_sk(int dt, const ConvGemmArgs &a, hipStream_t s);
-int conv_gemm_sk_variant(const ConvGemmArgs &a);
-bool conv_gemm_fast_ok(int dt, const ConvGemmArgs &a);
-bool conv_gemm_wp_ok(int dt, const ConvGemmArgs &a);
-bool conv_gemm_prefers_wp(const ConvGemmArgs &a);
-
-static bool use_sk(const ConvGemmArgs &a) {
-  const int v = pick_variant(a);
-  if (v <= 0 || (a.K % 32)) return false;
-  static const int bm[5] = {64, 128, 128, 64, 128}, bn[5] = {64, 32, 64, 64, 128};
-  const long blocks = (long)((a.M + bm[v] - 1) / bm[v]) * ((a.n_store + bn[v] - 1) / bn[v]);
-  return blocks < 256 && a.K >= 256;
-}
-
 // profiling label of a 16-bit kernel in the f16 build: the bf16 label with the type renamed (interned: labels are kept by pointer)
 const char *label_for_dtype(int dt, const char *bf16_label) {
   if (dt != F16) return bf16_label;
@@ -426,142 +475,177 @@ const char *label_for_dtype(int dt, const char *bf16_label) {
   return pool.insert(s).first->c_str();
 }
 
-static const char *variant_name_bf16(int dt, const ConvGemmArgs &a);
-// fp32 launches that carry split-fp16 weights: the families that honour them are labelled <x3,...> (the others multiply in fp32)
-static const char *label_x3(const ConvGemmArgs &a, const char *f32_label) {
-  if (!a.wx) return f32_label;
-  std::string s(f32_label);
-  if (s.rfind("conv_gemm_wp<f32", 0) != 0 && s.rfind("conv_gemm_fast<f32", 0) != 0) return f32_label;
-  static std::set<std::string> pool;
-  s.replace(s.find("f32"), 3, "x3");
-  return pool.insert(s).first->c_str();
-}
-const char *conv_gemm_variant_name(int dt, const ConvGemmArgs &a) {
-  return dt == F32 ? label_x3(a, variant_name_bf16(dt, a)) : label_for_dtype(dt, variant_name_bf16(dt, a));
-}
-// With a split image at hand (ConvGemmArgs::wx), does launch_conv_gemm(dt, a) take a kernel family that reads ONLY that image -- the
-// macro tiles, the wave-private / lean 32x32 kernels and the register-staged kernel in split mode, exactly the families label_x3() and
-// variant_name_bf16() label "<x3" -- so that ConvGemmArgs::w need not exist?  (The training step then packs no fp32 image and passes a
-// null `w`: a wrong answer here is a memory fault at address 0, not a wrong number.)
-bool conv_gemm_reads_split_only(int dt, const ConvGemmArgs &a_in) {
-  ConvGemmArgs a = a_in;
-  a.w = a.wx = reinterpret_cast<const void *>(16);   // probe: the decision depends on shapes and flags only
-  return std::strstr(conv_gemm_variant_name(dt, a), "<x3") != nullptr;
-}
-
-// Macro tiles pay from ~80 tiles of 256x128 per launch: a launch then occupies ~1/3 of the CUs at 4+ TFLOP/s each, and the
-// engine's second clip-parallel branch fills most of the rest (measured on BASELINE configs[2]: threshold 160 -> 138, 80 -> 145.5
-// steps/s; alone on the chip the 64x64 kernel still wins below ~160 tiles, tools/gemm_mt.py).  K >= 256: the three-slot ring
-// needs a few steps to reach steady state.
-static long short_act_tiles() {   // tuning hook: below this many 64x64 tiles a GEMM goes to the wave-split-K / wave-private kernels
-  static const long v = [] {
-    const char *e = tune_env("SF_SHORT_TILES");
-    const long t = e ? atol(e) : 0;
-    return t > 0 ? t : 500L;
-  }();
-  return v;
-}
-
-bool conv_gemm_prefers_mt(const ConvGemmArgs &a) {
-  static const int mode = [] {   // SF_MT=0 disables the kernel, SF_MT=2 prefers it wherever it is eligible (tuning / tests)
-    const char *e = tune_env("SF_MT");
-    return e ? atoi(e) : 1;
-  }();
-  if (mode == 0) return false;
-  if (mode == 2) return true;
-  static const int min_tiles = [] {   // tuning hook
-    const char *e = tune_env("SF_MT_TILES");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 40;   // re-measured with the later tile variants: batch 32 without guidance 218 (80) -> 230 (40) steps/s, batch 16 335 -> 341,
-                             // batch 32 with guidance and batch 8 unchanged
-  }();
-  // outputs of <= 64 columns: half-empty 128-wide tiles lose to the 64x64 kernel (346 vs 259 TFLOP/s on the onset net's 192 -> 64
-  // temporal convolution); the 128x64 tile with two workgroups per CU (video geometry) wins (542 vs 770 us on that shape)
-  if (a.n_store <= 64 && a.geom != 1) return false;
-  const long tiles = (long)((a.M + 127) / 128) * ((a.n_store + 127) / 128);   // the 128x128 variant takes over below 160 tiles of 256x128
-  // (shortest 1-D reduction: 256; 192 with the context padded to 64 columns was measured twice at -0.9 ... +1.6 % by workload and removed)
-  return tiles >= 2 * min_tiles && a.K >= (a.geom == 1 ? 128 : 256);   // two workgroups per CU cover the short pipelines of the video geometry
-}
-
-static const char *variant_name_bf16(int dt, const ConvGemmArgs &a) {
-  if (g_conv_gemm_force.path == 6 || (g_conv_gemm_force.path == 0 && conv_gemm_mt_wanted(dt, a))) return dt == F32 ? (a.wx ? "conv_gemm_mt<x3>" : "conv_gemm_mt<f32>") : conv_gemm_mt_name(a);
-  static const char *names[2][5] = {{"conv_gemm<f32,64x64,scalarA>", "conv_gemm<f32,128x32>", "conv_gemm<f32,128x64>", "conv_gemm<f32,64x64>", "conv_gemm<f32,128x128>"},
-                                    {"conv_gemm<bf16,64x64,scalarA>", "conv_gemm<bf16,128x32>", "conv_gemm<bf16,128x64>", "conv_gemm<bf16,64x64>", "conv_gemm<bf16,128x128>"}};
-  static const char *sk_names[2][3] = {{"conv_gemm_sk<f32,64x64>", "conv_gemm_sk<f32,64x32>", "conv_gemm_sk<f32,32x32>"},
-                                       {"conv_gemm_sk<bf16,64x64>", "conv_gemm_sk<bf16,64x32>", "conv_gemm_sk<bf16,32x32>"}};
-  static const char *fast_names[2][3] = {{"conv_gemm_fast<f32,64x64>", "conv_gemm_fast<f32,64x32>", "conv_gemm_fast<f32,32x32>"},
-                                         {"conv_gemm_fast<bf16,64x64>", "conv_gemm_fast<bf16,64x32>", "conv_gemm_fast<bf16,32x32>"}};
-  const long t64 = (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64);
-  const bool short_act = t64 < short_act_tiles() && a.K >= (a.short_k ? 128 : 256) && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
-  if (!short_act) {
-    V2Plan pl;
-    if (conv_gemm_v2_plan(dt, a, pl)) return conv_gemm_v2_name(dt, pl);
-  }
-  static const char *wp_names[2][3] = {{"conv_gemm_wp<f32,32x32>", "conv_gemm_wp<f32,32x32>", "conv_gemm_wp<f32,32x32>"},
-                                       {"conv_gemm_wp<bf16,64x64>", "conv_gemm_wp<bf16,64x32>", "conv_gemm_wp<bf16,32x32>"}};
-  if ((short_act || use_sk(a)) && conv_gemm_prefers_wp(a) && conv_gemm_sk_variant(a) == 2 && g_conv_gemm_force.path == 0 && conv_gemm_rs_ok(dt, a))
-    return dt == F32 ? "conv_gemm_rs<x3,32x32>" : "conv_gemm_rs<bf16,32x32>";
-  if ((short_act || use_sk(a)) && conv_gemm_prefers_wp(a) && conv_gemm_wp_ok(dt, a)) return wp_names[dt == F32 ? 0 : 1][conv_gemm_sk_variant(a)];
-  if (short_act || use_sk(a)) return (conv_gemm_fast_ok(dt, a) ? fast_names : sk_names)[dt == F32 ? 0 : 1][conv_gemm_sk_variant(a)];
-  int v = pick_variant(a);
-  return v < 0 ? "conv_gemm<invalid>" : names[dt == F32 ? 0 : 1][v];
-}
-
-ConvGemmForce g_conv_gemm_force;
-
-// Row-LayerNorm fusion on the macro tiles (row partials in the epilogue, LayerNorm on the accumulator): parity-tested at op level, but in
-// the two-branch step the launches it removes were hidden under the other branch's kernels and its epilogue work is not -- same-box A/B
-// (profiles/r5_c_ab_mt_ln.txt): configs[2] 202 -> 203.5 steps/s, batch 32 without guidance 301 -> 291.  Taken only when the caller asks
-// for it (ConvGemmArgs::mt_ln; the engine does not).
-
-bool conv_gemm_emits_rowpart(int dt, const ConvGemmArgs &a) {
-  if (g_conv_gemm_force.path != 0 || !conv_gemm_supported(dt, a)) return false;
-  {   // long activations: the macro-tile kernel; its epilogue writes the row partials for column counts that are multiples of 32
-    ConvGemmArgs plain = a;
-    plain.rowpart_out = nullptr;
-    if (conv_gemm_mt_wanted(dt, plain)) {
-      const bool off = a.mt_ln == 0;
-      ConvGemmArgs probe = a;   // (callers ask before they arm the launch)
-      if (!probe.rowpart_out) {
-        probe.rowpart_out = reinterpret_cast<float *>(16);
-        probe.rowpart_nt = a.n_store / 32;
+// The decision of launch_conv_gemm.  Automatic (ConvGemmForce::path == 0):
+//   macro tiles where eligible and preferred; otherwise long activations take v2 and short ones (fewer than short_act_tiles() tiles of
+//   64x64, or a classic tiling that would leave most CUs idle) the small-batch cascade rs -> wp -> fast -> sk; the classic tiles take the rest.
+// Forced (sf_bench_conv1d): 1 classic, 2 the cascade without rs / wp, 4 v2, 5 the cascade with wp preferred, 6 macro tiles; a forced launch
+// carries no fused epilogue statistics and no pre-split source.
+ConvGemmPlan conv_gemm_plan(int dt, const ConvGemmArgs &a) {
+  const ConvGemmForce &f = g_conv_gemm_force;
+  ConvGemmPlan p;
+  const bool automatic = f.path == 0;
+  if (!conv_gemm_supported(dt, a) || (a.src_x3 && !automatic)) return p;
+  if (f.path == 6 ? conv_gemm_mt_ok(dt, a) : (automatic && mt_wanted(dt, a))) {
+    p = mt_plan(dt, a);
+    p.src_x3 = automatic && a.src_x3;                                   // (conv_gemm_mt_ok has checked what the pre-split form needs)
+    p.rowpart = automatic && a.rowpart_out != nullptr && a.mt_ln != 0;   // the caller allows the row-LayerNorm fusion on the macro tiles
+  } else if (f.path == 6 || a.src_x3) {
+    return p;   // only the macro tiles read pre-split rows
+  } else {
+    // Macro tiles pay from ~80 tiles of 256x128 per launch (conv_gemm_mt.hip); below short_act_tiles() tiles of 64x64 the small-batch
+    // kernels win.  K >= 256: their pipelines need a few steps to reach steady state.
+    const long t64 = (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64);
+    const bool short_act = t64 < short_act_tiles() && a.K >= (a.short_k ? 128 : 256) && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
+    const int ct = classic_tile(a);
+    // the classic tiling would leave most CUs idle: the wave-split-K kernels
+    auto use_sk = [&] {
+      static const int bm[5] = {64, 128, 128, 64, 128}, bn[5] = {64, 32, 64, 64, 128};
+      return ct > 0 && (a.K % 32) == 0 && a.K >= 256 && (long)((a.M + bm[ct] - 1) / bm[ct]) * ((a.n_store + bn[ct] - 1) / bn[ct]) < 256;
+    };
+    if ((f.path == 4 || (automatic && !short_act)) && conv_gemm_v2_plan(dt, a, p.tile)) {
+      p.family = CG_V2;   // long activations: 2x2-wave tiles, channel counts that are multiples of 64, no prologue
+    } else if (f.path == 4) {
+      return p;
+    } else if (f.path == 2 || f.path == 5 || (automatic && (short_act || use_sk()))) {
+      if ((a.cin % 32) || (a.cin2 % 32) || (a.K % 32)) return p;
+      const int v = conv_gemm_sk_variant(a);
+      // barrier-free wave-private pipelines where few tiles exist (conv_gemm_prefers_wp); with many tiles the staged kernels win because
+      // their loads are shared by more MFMA work per byte
+      const bool wp_prefers = f.path == 5 || (automatic && conv_gemm_prefers_wp(a));
+      const bool wp = wp_prefers && conv_gemm_wp_ok(dt, a);
+      const int x3 = dt == F32 && a.wx ? (a.wx_mode == X3_BF16 ? X3_BF16 : X3_F16) : 0;
+      if (automatic && wp_prefers && v == 2 && conv_gemm_rs_ok(dt, a)) {
+        p.family = CG_RS;   // few 32x32 tiles and fragment-ordered weights at hand: all loads of a wave up front
+        p.tile = 0;
+        p.split = dt == F32 ? X3_F16 : 0;
+      } else if (wp && !(x3 == X3_BF16 && a.cin2)) {   // (the split bf16 form has one source: gradient GEMMs)
+        p.family = CG_WP;
+        p.tile = dt == F32 ? 2 : v;   // fp32 launches take the 32x32 tile
+        p.split = x3;
+      } else if (conv_gemm_fast_ok(dt, a)) {
+        p.family = CG_FAST;
+        p.tile = v;
+        p.split = dt == F32 && a.wx && (a.wx_mode == X3_F16 || (a.wx_mode == X3_BF16 && !a.cin2)) ? a.wx_mode : 0;
+        p.wide = !p.split && (a.cin % 256) == 0 && f.sk == 64;   // measured: no gain over 128-wide chunks
+      } else {
+        p.family = CG_SK;
+        p.tile = v;
       }
-      return !off && conv_gemm_mt_wanted(dt, probe);
+      // Epilogue statistics (32x32 tiles that hold whole 32-column groups).  A launch that the macro tiles would take without the row
+      // partials stays there: arming them must not move it.  (rs launches keep the rule of the kernels they took over from.)
+      const bool epi = automatic && v == 2 && p.family != CG_SK && (a.n_store % 32) == 0 && a.n_store == a.N && (wp || conv_gemm_fast_ok(dt, a)) &&
+                       !(a.rowpart_out && mt_wanted(dt, without_rowpart(a)));
+      p.rowpart = epi;
+      p.gnpart = epi && wp && p.family != CG_FAST && a.Lout >= 32;   // wp / rs write them: a tile touches at most two clips
+    } else if (ct >= 0) {
+      p.family = CG_CLASSIC;
+      p.tile = ct;
     }
   }
-  if ((a.n_store % 32) || a.n_store != a.N) return false;
-  const long t64 = (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64);
-  const bool short_act = t64 < short_act_tiles() && a.K >= (a.short_k ? 128 : 256) && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
-  if (!(short_act || use_sk(a))) return false;                 // would go to v2 / the classic tiles
-  if ((a.cin % 32) || (a.cin2 % 32) || (a.K % 32)) return false;
-  if (conv_gemm_sk_variant(a) != 2) return false;              // 32x32 tiles only
-  const bool prefer_wp = conv_gemm_prefers_wp(a);
-  if (prefer_wp && conv_gemm_wp_ok(dt, a)) return true;        // wp 32x32 (its LDS footprint fits in both types)
-  return conv_gemm_fast_ok(dt, a);
+  p.label = plan_label(dt, p);
+  return p;
 }
 
-bool conv_gemm_emits_gnpart(int dt, const ConvGemmArgs &a) {
+// The decision of launch_conv_gemm_ln: the first source (cin channels, one tap) is LayerNorm-modulated on the fly from row partials.
+ConvGemmPlan conv_gemm_ln_plan(int dt, const ConvGemmArgs &a) {
+  ConvGemmPlan p;
+  p.ln = true;
   ConvGemmArgs plain = a;
-  plain.gnpart_out = nullptr;
-  if (a.geom != 0 || a.Lout < 32 || !conv_gemm_emits_rowpart(dt, plain)) return false;
-  return conv_gemm_prefers_wp(a) && conv_gemm_wp_ok(dt, a);   // the wave-private 32x32 kernel is the one that writes them
+  plain.ln_part = nullptr;
+  plain.ln_colsum = nullptr;
+  plain.ln_ss = nullptr;
+  plain.rowpart_out = nullptr;
+  plain.res_ln = 0;
+  const bool acc_side = a.ln_colsum && !a.ln_ss && !a.res_ln;   // LayerNorm applied to the accumulator: raw rows through the matrix cores
+  if (mt_wanted(dt, plain)) {
+    // long activations: the macro-tile GEMM beats the LayerNorm-fused 32x32 kernel; it carries the accumulator-side LayerNorm but no
+    // operand transform (Modulation + InjectChannels keep their ln_modulate launch there), and only where the caller allows it
+    if (a.mt_ln == 0 || !a.ln_part || !acc_side || !conv_gemm_mt_ok(dt, a)) return p;
+    const bool rowpart = a.rowpart_out != nullptr;
+    p = mt_plan(dt, a);
+    p.ln = true;
+    p.rowpart = rowpart;
+  } else {
+    if (!conv_gemm_fast_ok(dt, a)) return p;
+    // the operand-transform form runs on the 32x32 staged kernel: short activations only (with the macro-tile row partials a long
+    // producer can offer them too -- depth 3 at batch 32: 8 launches of 13 us more than ln_modulate + the 64x64 kernel)
+    if (!acc_side && (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64) >= 500) return p;
+    if (a.taps != 1 || a.stride != 1 || a.up_shift != 0 || a.Lout != a.Lsrc || a.Lout < 32) return p;
+    if (!a.ln_part || a.ln_nt * 32 != a.cin || a.ln_nt > 32) return p;
+    if (a.res_ln && (a.N != a.cin || !a.res)) return p;
+    if (a.ln_colsum && (a.cin2 || a.ln_ss || a.res_ln)) return p;
+    if (a.rowpart_out && ((a.n_store % 32) || a.rowpart_nt * 32 != a.n_store)) return p;
+    static const long rs_max_tiles = [] {   // tuning hook: most 32x32 tiles a LayerNorm-folded projection may have and still take the register-staged kernel
+      const char *e = tune_env("SF_RS_LN_TILES");
+      return e ? atol(e) : 512L;
+    }();
+    // tuning hook: the wave-private kernel also carries the epilogue fold, but on the qkv projections of this model (288 tiles,
+    // K = 1024) the staged kernel measured 1.2 % faster over a whole step (460 vs 455 steps/s), so it stays opt-in
+    static const bool use_wp = tune_env("SF_LN_WP") != nullptr;
+    const long tiles = (long)((a.M + 31) / 32) * ((a.n_store + 31) / 32);
+    const int x3 = dt == F32 && a.wx ? (a.wx_mode == X3_BF16 ? X3_BF16 : X3_F16) : 0;
+    p.tile = 2;
+    p.rowpart = a.rowpart_out != nullptr;
+    if (acc_side && g_conv_gemm_force.path == 0 && tiles <= rs_max_tiles && a.K >= 256 && conv_gemm_rs_ok(dt, a)) {
+      p.family = CG_RS;   // fragment-ordered weights at hand and few tiles
+      p.tile = 0;
+      p.split = dt == F32 ? X3_F16 : 0;
+    } else if (use_wp && acc_side && !a.rowpart_out && conv_gemm_wp_ok(dt, a)) {
+      p.family = CG_WP;
+      p.split = x3;
+    } else {
+      p.family = CG_FAST;
+      p.split = x3 == X3_F16 ? X3_F16 : 0;
+    }
+  }
+  p.label = plan_label(dt, p);
+  return p;
 }
 
-hipError_t launch_conv_gemm(int dt, const ConvGemmArgs &a, hipStream_t s) {
-  if (!conv_gemm_supported(dt, a)) return hipErrorInvalidValue;
-  if (a.src_x3 && (dt != F32 || g_conv_gemm_force.path != 0 || !conv_gemm_src_x3_ok(a))) return hipErrorInvalidValue;   // only the macro tiles read pre-split rows
-  const ConvGemmForce &f = g_conv_gemm_force;
-  if (f.path == 6) return launch_conv_gemm_mt(dt, a, s);
-  if (f.path == 0 && conv_gemm_mt_wanted(dt, a)) return launch_conv_gemm_mt(dt, a, s);
-  const long t64 = (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64);
-  const bool short_act = t64 < short_act_tiles() && a.K >= (a.short_k ? 128 : 256) && (a.K % 32) == 0 && (a.cin % 32) == 0 && (a.cin2 % 32) == 0;
-  if (f.path == 4 || (f.path == 0 && !short_act)) {
-    V2Plan pl;   // long activations: classic 2x2-wave tiles, channel counts that are multiples of 64, no prologue
-    if (conv_gemm_v2_plan(dt, a, pl)) return launch_conv_gemm_v2(dt, a, pl, s);
-    if (f.path == 4) return hipErrorInvalidValue;
+hipError_t launch_conv_gemm_planned(int dt, const ConvGemmArgs &a, const ConvGemmPlan &p, hipStream_t s) {
+  switch (p.family) {
+    case CG_CLASSIC: return SF_DISPATCH_T(dt, launch_classic<T>(a, p.tile, s));
+    case CG_V2: return launch_conv_gemm_v2(dt, a, p.tile, s);
+    case CG_SK: return launch_conv_gemm_sk(dt, a, p.tile, s);
+    case CG_FAST: return launch_conv_gemm_fast(dt, a, p, s);
+    case CG_WP: return launch_conv_gemm_wp(dt, a, p.tile, p.split, s);
+    case CG_RS: return launch_conv_gemm_rs(dt, a, s);
+    case CG_MT: return launch_conv_gemm_mt(dt, a, p.tile, p.split, s);
+    default: return hipErrorInvalidValue;
   }
-  if (f.path == 2 || f.path == 5 || (f.path == 0 && (short_act || use_sk(a)))) return launch_conv_gemm_sk(dt, a, s);
-  return SF_DISPATCH_T(dt, dispatch<T>(a, s));
+}
+hipError_t launch_conv_gemm(int dt, const ConvGemmArgs &a, hipStream_t s) { return launch_conv_gemm_planned(dt, a, conv_gemm_plan(dt, a), s); }
+hipError_t launch_conv_gemm_ln(int dt, const ConvGemmArgs &a, hipStream_t s) { return launch_conv_gemm_planned(dt, a, conv_gemm_ln_plan(dt, a), s); }
+
+const char *conv_gemm_variant_name(int dt, const ConvGemmArgs &a) { return conv_gemm_plan(dt, a).label; }
+const char *conv_gemm_ln_variant_name(int dt, const ConvGemmArgs &a) { return conv_gemm_ln_plan(dt, a).label; }
+bool conv_gemm_ln_ok(int dt, const ConvGemmArgs &a) { return conv_gemm_ln_plan(dt, a).family != CG_INVALID; }
+
+// The queries below are asked before the caller sets the pointer or flag in question: each arms its copy and reads the plan.
+// (A wrong answer of conv_gemm_reads_split_only is a memory fault, not a wrong number: the training step then packs no fp32 image and
+// passes a null `w`.)
+bool conv_gemm_reads_split_only(int dt, const ConvGemmArgs &a_in) {
+  ConvGemmArgs a = a_in;
+  if (!a.wx) a.wx = g_armed;
+  return conv_gemm_plan(dt, a).split != 0;
+}
+bool conv_gemm_emits_rowpart(int dt, const ConvGemmArgs &a_in) {
+  ConvGemmArgs a = a_in;
+  if (!a.rowpart_out) {
+    a.rowpart_out = g_armed;
+    a.rowpart_nt = a.n_store / 32;
+  }
+  return conv_gemm_plan(dt, a).rowpart;
+}
+bool conv_gemm_emits_gnpart(int dt, const ConvGemmArgs &a_in) {
+  ConvGemmArgs a = a_in;
+  if (!a.gnpart_out) a.gnpart_out = g_armed;
+  return conv_gemm_plan(dt, a).gnpart;
+}
+bool conv_gemm_src_x3_ok(const ConvGemmArgs &a_in) {
+  ConvGemmArgs a = a_in;
+  a.src_x3 = 1;
+  return conv_gemm_plan(F32, a).src_x3;
 }
 
 }  // namespace sf

@@ -463,8 +463,28 @@ template <typename T, int BM, int BN, bool CAT, int KW, int NSET, bool LN = fals
 
 // Two chunks in flight: measured with HBM-cold weights (tools/gemm_cold.py), 4 or 6 chunks in flight are no faster
 // (the limit is the L2 -> CU fill rate, ~25 B/clk/CU here, not latency) and 6 cost occupancy.
-template <typename T, int BM, int BN, bool CAT, int KW> hipError_t launch_fast2(const ConvGemmArgs &a, hipStream_t s) {
-  return launch_fast3<T, BM, BN, CAT, KW, 2>(a, s);
+// 256-wide chunks (KW = 64: 64 K per wave and iteration, half the barriers) exist for the plain form only.
+template <typename T, int BM, int BN, int KW, int X3 = 0> hipError_t launch_fast_cat(const ConvGemmArgs &a, hipStream_t s) {
+  return a.cin2 ? launch_fast3<T, BM, BN, true, KW, 2, false, X3>(a, s) : launch_fast3<T, BM, BN, false, KW, 2, false, X3>(a, s);
+}
+template <typename T, int BM, int BN> hipError_t launch_fast_tile(const ConvGemmArgs &a, const ConvGemmPlan &p, hipStream_t s) {
+  if constexpr (sizeof(T) == 4) {   // split operands: fp32 launches only
+    if (p.split == X3_BF16) return launch_fast3<T, BM, BN, false, 32, 2, false, X3_BF16>(a, s);   // gradients: one source
+    if (p.split == X3_F16) return launch_fast_cat<T, BM, BN, 32, X3_F16>(a, s);
+  }
+  return p.wide ? launch_fast_cat<T, BM, BN, 64>(a, s) : launch_fast_cat<T, BM, BN, 32>(a, s);
+}
+template <typename T> hipError_t launch_fast(const ConvGemmArgs &a, const ConvGemmPlan &p, hipStream_t s) {
+  if (p.ln) {   // consumer-side row LayerNorm: 32x32 tiles
+    if constexpr (sizeof(T) == 4)
+      if (p.split == X3_F16) return a.cin2 ? launch_fast3<T, 32, 32, true, 32, 2, true, X3_F16>(a, s) : launch_fast3<T, 32, 32, false, 32, 2, true, X3_F16>(a, s);
+    return a.cin2 ? launch_fast3<T, 32, 32, true, 32, 2, true>(a, s) : launch_fast3<T, 32, 32, false, 32, 2, true>(a, s);
+  }
+  switch (p.tile) {
+    case 0: return launch_fast_tile<T, 64, 64>(a, p, s);
+    case 1: return launch_fast_tile<T, 64, 32>(a, p, s);
+    default: return launch_fast_tile<T, 32, 32>(a, p, s);
+  }
 }
 
 }  // namespace
@@ -482,120 +502,6 @@ bool conv_gemm_fast_ok(int dt, const ConvGemmArgs &a) {
   return true;
 }
 
-// long activations: the macro-tile GEMM beats the LayerNorm-fused 32x32 kernel; it carries the accumulator-side LayerNorm (ln_colsum)
-// but no operand transform (Modulation + InjectChannels keep their ln_modulate launch there)
-static bool ln_goes_mt(int dt, const ConvGemmArgs &a, bool *supported = nullptr) {
-  ConvGemmArgs plain = a;
-  plain.ln_part = nullptr;
-  plain.ln_colsum = nullptr;
-  plain.ln_ss = nullptr;
-  plain.rowpart_out = nullptr;
-  plain.res_ln = 0;
-  if (!conv_gemm_mt_wanted(dt, plain)) return false;
-  const bool off = a.mt_ln == 0;
-  if (supported) *supported = !off && a.ln_part && a.ln_colsum && !a.ln_ss && !a.res_ln && conv_gemm_mt_ok(dt, a);
-  return true;
-}
-
-bool conv_gemm_ln_ok(int dt, const ConvGemmArgs &a) {
-  {
-    bool sup = false;
-    if (ln_goes_mt(dt, a, &sup)) return sup;
-  }
-  if (!conv_gemm_fast_ok(dt, a)) return false;
-  // the operand-transform form runs on the 32x32 staged kernel: short activations only (with the macro-tile row partials a long
-  // producer can offer them too -- depth 3 at batch 32: 8 launches of 13 us more than ln_modulate + the 64x64 kernel)
-  if ((a.ln_ss || a.res_ln || !a.ln_colsum) && (long)((a.M + 63) / 64) * ((a.n_store + 63) / 64) >= 500) return false;
-  if (a.taps != 1 || a.stride != 1 || a.up_shift != 0 || a.Lout != a.Lsrc || a.Lout < 32) return false;
-  if (!a.ln_part || a.ln_nt * 32 != a.cin || a.ln_nt > 32) return false;
-  if (a.res_ln && (a.N != a.cin || !a.res)) return false;
-  if (a.ln_colsum && (a.cin2 || a.ln_ss || a.res_ln)) return false;
-  if (a.rowpart_out && ((a.n_store % 32) || a.rowpart_nt * 32 != a.n_store)) return false;
-  return true;
-}
-
-bool conv_gemm_wp_ok(int dt, const ConvGemmArgs &a);                                           // conv_gemm_wp.hip
-hipError_t launch_conv_gemm_wp(int dt, const ConvGemmArgs &a, int variant, hipStream_t s);
-
-static bool ln_goes_wp(int dt, const ConvGemmArgs &a) {
-  // tuning hook: the wave-private kernel also carries the epilogue fold, but on the qkv projections of this model (288 tiles,
-  // K = 1024) the staged kernel measured 1.2 % faster over a whole step (460 vs 455 steps/s), so it stays opt-in
-  static const bool use_wp = tune_env("SF_LN_WP") != nullptr;
-  return use_wp && a.ln_colsum && !a.ln_ss && !a.res_ln && !a.rowpart_out && conv_gemm_wp_ok(dt, a);
-}
-
-static bool ln_goes_rs(int dt, const ConvGemmArgs &a);
-const char *conv_gemm_ln_variant_name(int dt, const ConvGemmArgs &a) {
-  if (ln_goes_mt(dt, a)) return label_for_dtype(dt, conv_gemm_mt_name(a));
-  if (ln_goes_rs(dt, a)) return dt == F32 ? "conv_gemm_rs<x3,32x32>" : label_for_dtype(dt, "conv_gemm_rs<bf16,32x32>");
-  if (dt == F32 && a.wx && a.wx_mode == X3_F16) return ln_goes_wp(dt, a) ? "conv_gemm_wp<x3,32x32>" : "conv_gemm_fast<x3,32x32>";
-  if (dt == F32) return ln_goes_wp(dt, a) ? "conv_gemm_wp<f32,32x32>" : "conv_gemm_fast<f32,32x32>";
-  return label_for_dtype(dt, ln_goes_wp(dt, a) ? "conv_gemm_wp<bf16,32x32>" : "conv_gemm_fast<bf16,32x32>");
-}
-
-// the accumulator-side LayerNorm (raw rows through the matrix cores, rstd * (acc - mean * colsum) in the epilogue) on the register-staged
-// kernel when the fragment-ordered weights are at hand and the launch has few tiles
-bool conv_gemm_prefers_wp(const ConvGemmArgs &a);
-static bool ln_goes_rs(int dt, const ConvGemmArgs &a) {
-  static const long max_tiles = [] {   // tuning hook: most 32x32 tiles a LayerNorm-folded projection may have and still take the register-staged kernel
-    const char *e = tune_env("SF_RS_LN_TILES");
-    return e ? atol(e) : 512L;
-  }();
-  const long tiles = (long)((a.M + 31) / 32) * ((a.n_store + 31) / 32);
-  return a.ln_colsum && !a.ln_ss && !a.res_ln && g_conv_gemm_force.path == 0 && tiles <= max_tiles && a.K >= 256 && conv_gemm_rs_ok(dt, a);
-}
-
-hipError_t launch_conv_gemm_ln(int dt, const ConvGemmArgs &a, hipStream_t s) {
-  if (!conv_gemm_ln_ok(dt, a)) return hipErrorInvalidValue;
-  if (ln_goes_mt(dt, a)) return launch_conv_gemm_mt(dt, a, s);
-  if (ln_goes_rs(dt, a)) return launch_conv_gemm_rs(dt, a, s);
-  if (ln_goes_wp(dt, a)) return launch_conv_gemm_wp(dt, a, 2, s);
-  if (dt == F32 && a.wx && a.wx_mode == X3_F16) return a.cin2 ? launch_fast3<float, 32, 32, true, 32, 2, true, X3_F16>(a, s) : launch_fast3<float, 32, 32, false, 32, 2, true, X3_F16>(a, s);
-  return SF_DISPATCH_T(dt, (a.cin2 ? launch_fast3<T, 32, 32, true, 32, 2, true>(a, s) : launch_fast3<T, 32, 32, false, 32, 2, true>(a, s)));
-}
-
-hipError_t launch_conv_gemm_fast(int dt, const ConvGemmArgs &a, int variant, hipStream_t s) {
-  // 256-wide chunks (64 K per wave and iteration: half the barriers) when the channel count allows it
-  const bool wide = (a.cin % 256) == 0 && g_conv_gemm_force.sk == 64;   // measured: no gain over 128-wide chunks
-#define SF_FAST(T, BM, BN)                                                                                              \
-  (wide ? (a.cin2 ? launch_fast2<T, BM, BN, true, 64>(a, s) : launch_fast2<T, BM, BN, false, 64>(a, s))                 \
-        : (a.cin2 ? launch_fast2<T, BM, BN, true, 32>(a, s) : launch_fast2<T, BM, BN, false, 32>(a, s)))
-  if (dt == F32 && a.wx && a.wx_mode == X3_BF16 && !a.cin2) {   // split mode, gradients
-    switch (variant) {
-      case 0: return launch_fast3<float, 64, 64, false, 32, 2, false, X3_BF16>(a, s);
-      case 1: return launch_fast3<float, 64, 32, false, 32, 2, false, X3_BF16>(a, s);
-      default: return launch_fast3<float, 32, 32, false, 32, 2, false, X3_BF16>(a, s);
-    }
-  }
-  if (dt == F32 && a.wx && a.wx_mode == X3_F16) {   // split mode
-#define SF_FASTX(BM, BN) (a.cin2 ? launch_fast3<float, BM, BN, true, 32, 2, false, X3_F16>(a, s) : launch_fast3<float, BM, BN, false, 32, 2, false, X3_F16>(a, s))
-    switch (variant) {
-      case 0: return SF_FASTX(64, 64);
-      case 1: return SF_FASTX(64, 32);
-      default: return SF_FASTX(32, 32);
-    }
-#undef SF_FASTX
-  }
-  if (dt == F32) {
-    switch (variant) {
-      case 0: return SF_FAST(float, 64, 64);
-      case 1: return SF_FAST(float, 64, 32);
-      default: return SF_FAST(float, 32, 32);
-    }
-  }
-  if (dt == F16) {
-    switch (variant) {
-      case 0: return SF_FAST(f16, 64, 64);
-      case 1: return SF_FAST(f16, 64, 32);
-      default: return SF_FAST(f16, 32, 32);
-    }
-  }
-  switch (variant) {
-    case 0: return SF_FAST(bf16, 64, 64);
-    case 1: return SF_FAST(bf16, 64, 32);
-    default: return SF_FAST(bf16, 32, 32);
-  }
-#undef SF_FAST
-}
+hipError_t launch_conv_gemm_fast(int dt, const ConvGemmArgs &a, const ConvGemmPlan &p, hipStream_t s) { return SF_DISPATCH_T(dt, launch_fast<T>(a, p, s)); }
 
 }  // namespace sf

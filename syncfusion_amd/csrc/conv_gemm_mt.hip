@@ -634,10 +634,22 @@ template <bool CAT, int MODE, bool AX = false> hipError_t launch_mt_x3(const Con
   }
 }
 
+// split form: one source for the bf16 split (gradient GEMMs) and for pre-split rows (ConvGemmArgs::src_x3) -- conv_gemm_mt_ok
+template <typename T> hipError_t launch_mt_t(const ConvGemmArgs &a, int tile, int split, hipStream_t s) {
+  if constexpr (sizeof(T) == 4) {
+    if (split == X3_BF16) return launch_mt_x3<false, X3_BF16>(a, tile, s);
+    if (split == X3_F16 && a.src_x3) return launch_mt_x3<false, X3_F16, true>(a, tile, s);
+    if (split == X3_F16) return a.cin2 ? launch_mt_x3<true, X3_F16>(a, tile, s) : launch_mt_x3<false, X3_F16>(a, tile, s);
+  } else {
+    if (a.geom == 1) return launch_mt_v<T, 1, false>(a, tile, s);   // video geometry: the 16-bit types, one source
+  }
+  return a.cin2 ? launch_mt_v<T, 0, true>(a, tile, s) : launch_mt_v<T, 0, false>(a, tile, s);
+}
+
 }  // namespace
 
-int conv_gemm_mt_variant(const ConvGemmArgs &a);
-// eligibility (what the kernel implements) -- the CHOICE between this kernel and conv_gemm_v2 is conv_gemm_prefers_mt
+static int conv_gemm_mt_variant(const ConvGemmArgs &a);
+// eligibility (what the kernel implements) -- the CHOICE between this kernel and the others is conv_gemm_mt_prefers
 bool conv_gemm_mt_ok(int dt, const ConvGemmArgs &a) {
   const size_t es = dt == F32 ? 4 : 2;
   const int bke = (int)(ROWB / es), vec = (int)(16 / es);   // elements per K step / per 16-byte access
@@ -669,7 +681,7 @@ bool conv_gemm_mt_ok(int dt, const ConvGemmArgs &a) {
 // 128x64 (three slots, two workgroups per CU) below 512 tiles of 128x128, 128x128 (two slots, two per CU) above.  Alone on the chip
 // (tools/gemm_f32.py, batch 4 x 2^18 samples): 16384 x 128 x 384 25.3 -> 19.3 us, 8192 x 256 x 768 39.3 -> 32.9, 4096 x 512 x 1536 66.5 -> 60.1,
 // 8192 x 1536 x 256 137.7 -> 62.0, 4096 x 1536 x 512 126.2 -> 58.6 us (110 TFLOP/s of the 157 fp32 peak).
-bool conv_gemm_prefers_mt_f32(const ConvGemmArgs &a) {
+static bool conv_gemm_prefers_mt_f32(const ConvGemmArgs &a) {
   static const long min_tiles = [] {   // tuning hook: SF_MT_F32_TILES=0 keeps fp32 off the macro tiles
     const char *e = tune_env("SF_MT_F32_TILES");
     return e ? atol(e) : 256L;   // a full round of 128x64 tiles: at 128 tiles the wave-split-K / 64x64 kernels win (41 vs 57 us, 71 vs 110 us)
@@ -700,15 +712,34 @@ static int conv_gemm_mt_x3_variant(const ConvGemmArgs &a) {
   if (a.solo && (long)((a.M + 127) / 128) * ((a.n_store + 127) / 128) < 256 && a.n_store % 64 == 0) return 7;
   return 5;
 }
-bool conv_gemm_src_x3_ok(const ConvGemmArgs &a) {
-  ConvGemmArgs p = a;
-  p.src_x3 = 0;
-  return a.wx && a.wx_mode == X3_F16 && !a.cin2 && a.geom == 0 && conv_gemm_mt_wanted(F32, p);
+// the 16-bit types
+static bool conv_gemm_prefers_mt_16(const ConvGemmArgs &a) {
+  static const int mode = [] {   // SF_MT=0 disables the kernel, SF_MT=2 prefers it wherever it is eligible (tuning / tests)
+    const char *e = tune_env("SF_MT");
+    return e ? atoi(e) : 1;
+  }();
+  if (mode == 0) return false;
+  if (mode == 2) return true;
+  // Macro tiles pay from ~80 tiles of 256x128 per launch: a launch then occupies ~1/3 of the CUs at 4+ TFLOP/s each, and the
+  // engine's second clip-parallel branch fills most of the rest (measured on BASELINE configs[2]: threshold 160 -> 138, 80 -> 145.5
+  // steps/s; alone on the chip the 64x64 kernel still wins below ~160 tiles, tools/gemm_mt.py).  K >= 256: the three-slot ring
+  // needs a few steps to reach steady state.
+  static const int min_tiles = [] {   // tuning hook
+    const char *e = tune_env("SF_MT_TILES");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 ? v : 40;   // re-measured with the later tile variants: batch 32 without guidance 218 (80) -> 230 (40) steps/s, batch 16 335 -> 341,
+                             // batch 32 with guidance and batch 8 unchanged
+  }();
+  // outputs of <= 64 columns: half-empty 128-wide tiles lose to the 64x64 kernel (346 vs 259 TFLOP/s on the onset net's 192 -> 64
+  // temporal convolution); the 128x64 tile with two workgroups per CU (video geometry) wins (542 vs 770 us on that shape)
+  if (a.n_store <= 64 && a.geom != 1) return false;
+  const long tiles = (long)((a.M + 127) / 128) * ((a.n_store + 127) / 128);   // the 128x128 variant takes over below 160 tiles of 256x128
+  // (shortest 1-D reduction: 256; 192 with the context padded to 64 columns was measured twice at -0.9 ... +1.6 % by workload and removed)
+  return tiles >= 2 * min_tiles && a.K >= (a.geom == 1 ? 128 : 256);   // two workgroups per CU cover the short pipelines of the video geometry
 }
-bool conv_gemm_mt_wanted(int dt, const ConvGemmArgs &a) {
-  if (!conv_gemm_mt_ok(dt, a)) return false;
-  if (dt == F32 && a.wx) return conv_gemm_prefers_mt_x3(a);
-  return dt == F32 ? conv_gemm_prefers_mt_f32(a) : conv_gemm_prefers_mt(a);
+bool conv_gemm_mt_prefers(int dt, const ConvGemmArgs &a) {
+  if (dt == F32) return a.wx ? conv_gemm_prefers_mt_x3(a) : conv_gemm_prefers_mt_f32(a);
+  return conv_gemm_prefers_mt_16(a);
 }
 
 // tile variant: 0 = 256x128, 1 = 128x128, 2 = 128x192, 3 = 192x128, 4 = 256x64 (three-slot ring, one workgroup per CU);
@@ -788,30 +819,15 @@ int conv_gemm_mt_variant(const ConvGemmArgs &a) {
   return t256 < 160 ? 1 : 0;                                   // few row bands: halve the tile so that more CUs get one
 }
 
-const char *conv_gemm_mt_name(const ConvGemmArgs &a) {
-  static const char *n[11] = {"conv_gemm_mt<bf16,256x128>", "conv_gemm_mt<bf16,128x128>", "conv_gemm_mt<bf16,128x192>", "conv_gemm_mt<bf16,192x128>",
-                             "conv_gemm_mt<bf16,256x64>", "conv_gemm_mt<bf16,128x128,2wg>", "conv_gemm_mt<bf16,128x192,2wg>", "conv_gemm_mt<bf16,128x64,2wg>",
-                             "conv_gemm_mt<bf16,192x128,2wg>", "conv_gemm_mt<bf16,256x64,2wg>", "conv_gemm_mt<bf16,256x256>"};
-  return n[conv_gemm_mt_variant(a)];
+// the tile of a launch: the 16-bit rule above, the split-mode rule, or the fp32 rule
+int conv_gemm_mt_tile(int dt, const ConvGemmArgs &a) {
+  if (dt != F32) return conv_gemm_mt_variant(a);
+  if (a.wx) return conv_gemm_mt_x3_variant(a);
+  static const int forced = [] { const char *e = tune_env("SF_MT_F32_VARIANT"); return e ? atoi(e) : -1; }();   // tuning hook: 1, 5, 7
+  const long t128 = (long)((a.M + 127) / 128) * ((a.n_store + 127) / 128);
+  return forced >= 0 ? forced : ((a.n_store % 64 == 0 && t128 < 512) ? 7 : 5);
 }
 
-hipError_t launch_conv_gemm_mt(int dt, const ConvGemmArgs &a, hipStream_t s) {
-  if (!conv_gemm_mt_ok(dt, a)) return hipErrorInvalidValue;
-  if (dt == F32 && a.wx) {
-    const int v = conv_gemm_mt_x3_variant(a);
-    if (a.wx_mode == X3_BF16) return (a.cin2 || a.src_x3) ? hipErrorInvalidValue : launch_mt_x3<false, X3_BF16>(a, v, s);   // (gradient GEMMs have one source)
-    if (a.src_x3) return a.cin2 ? hipErrorInvalidValue : launch_mt_x3<false, X3_F16, true>(a, v, s);
-    return a.cin2 ? launch_mt_x3<true, X3_F16>(a, v, s) : launch_mt_x3<false, X3_F16>(a, v, s);
-  }
-  if (dt == F32) {
-    static const int forced = [] { const char *e = tune_env("SF_MT_F32_VARIANT"); return e ? atoi(e) : -1; }();   // tuning hook: 1, 5, 7
-    const long t128 = (long)((a.M + 127) / 128) * ((a.n_store + 127) / 128);
-    const int v = forced >= 0 ? forced : ((a.n_store % 64 == 0 && t128 < 512) ? 7 : 5);
-    return a.cin2 ? launch_mt_v<float, 0, true>(a, v, s) : launch_mt_v<float, 0, false>(a, v, s);
-  }
-  const int v = conv_gemm_mt_variant(a);
-  if (dt == F16) return a.geom == 1 ? launch_mt_v<f16, 1, false>(a, v, s) : (a.cin2 ? launch_mt_v<f16, 0, true>(a, v, s) : launch_mt_v<f16, 0, false>(a, v, s));
-  return a.geom == 1 ? launch_mt_v<bf16, 1, false>(a, v, s) : (a.cin2 ? launch_mt_v<bf16, 0, true>(a, v, s) : launch_mt_v<bf16, 0, false>(a, v, s));
-}
+hipError_t launch_conv_gemm_mt(int dt, const ConvGemmArgs &a, int tile, int split, hipStream_t s) { return SF_DISPATCH_T(dt, launch_mt_t<T>(a, tile, split, s)); }
 
 }  // namespace sf

@@ -388,8 +388,8 @@ hipError_t launch_pack_wfrx(const float *w, int N, int K, void *out, hipStream_t
   return hipGetLastError();
 }
 
+// (fp32 launches: the split-operand form -- conv_gemm_rs_ok admits no other)
 hipError_t launch_conv_gemm_rs(int dt, const ConvGemmArgs &a, hipStream_t s) {
-  if (!conv_gemm_rs_ok(dt, a)) return hipErrorInvalidValue;
   if (dt == F32) return a.cin2 ? launch_rs_x3<true>(a, s) : launch_rs_x3<false>(a, s);
   if (dt == BF16) return a.cin2 ? launch_rs<bf16, true>(a, s) : launch_rs<bf16, false>(a, s);
   return a.cin2 ? launch_rs<f16, true>(a, s) : launch_rs<f16, false>(a, s);

@@ -352,6 +352,14 @@ template <typename T, int BM, int BN> hipError_t launch_sk(const ConvGemmArgs &a
   return launch_sk2<T, BM, BN, 0, false, false>(a, s);
 }
 
+template <typename T> hipError_t launch_sk_tile(const ConvGemmArgs &a, int tile, hipStream_t s) {
+  switch (tile) {
+    case 0: return launch_sk<T, 64, 64>(a, s);
+    case 1: return launch_sk<T, 64, 32>(a, s);
+    default: return launch_sk<T, 32, 32>(a, s);
+  }
+}
+
 }  // namespace
 
 // tile choice: the largest of 64x64 / 64x32 / 32x32 that still yields >= 224 workgroups
@@ -374,12 +382,6 @@ int conv_gemm_sk_variant(const ConvGemmArgs &a) {
   return 0;
 }
 
-bool conv_gemm_fast_ok(int dt, const ConvGemmArgs &a);
-hipError_t launch_conv_gemm_fast(int dt, const ConvGemmArgs &a, int variant, hipStream_t s);
-bool conv_gemm_wp_ok(int dt, const ConvGemmArgs &a);
-hipError_t launch_conv_gemm_wp(int dt, const ConvGemmArgs &a, int variant, hipStream_t s);
-
-bool conv_gemm_prefers_wp(const ConvGemmArgs &a);
 bool conv_gemm_rs_rows_ok(int64_t rows, int N) {
   ConvGemmArgs a;
   a.M = (int)rows;
@@ -401,38 +403,6 @@ bool conv_gemm_prefers_wp(const ConvGemmArgs &a) {
   return (tiles <= max_tiles && a.K >= 256) || (a.M <= 512 && a.K >= 2048);
 }
 
-hipError_t launch_conv_gemm_sk(int dt, const ConvGemmArgs &a, hipStream_t s) {
-  if ((a.cin % 32) || (a.cin2 % 32) || (a.K % 32)) return hipErrorInvalidValue;
-  const int v = conv_gemm_sk_variant(a);
-  // barrier-free wave-private pipelines where few tiles exist (conv_gemm_prefers_wp); with many tiles the staged kernel
-  // wins because its loads are shared by more MFMA work per byte
-  const bool prefer_wp = g_conv_gemm_force.path == 5 || (g_conv_gemm_force.path == 0 && conv_gemm_prefers_wp(a));
-  // few 32x32 tiles and fragment-ordered weights at hand: the register-staged kernel (all loads of a wave up front)
-  if (g_conv_gemm_force.path == 0 && prefer_wp && v == 2 && conv_gemm_rs_ok(dt, a)) return launch_conv_gemm_rs(dt, a, s);
-  if (prefer_wp && conv_gemm_wp_ok(dt, a)) {
-    hipError_t e = launch_conv_gemm_wp(dt, a, dt == F32 ? 2 : v, s);
-    if (e != hipErrorInvalidValue) return e;
-  }
-  if (conv_gemm_fast_ok(dt, a)) return launch_conv_gemm_fast(dt, a, v, s);   // lean path (conv_gemm_fast.hip)
-  if (dt == F32) {
-    switch (v) {
-      case 0: return launch_sk<float, 64, 64>(a, s);
-      case 1: return launch_sk<float, 64, 32>(a, s);
-      default: return launch_sk<float, 32, 32>(a, s);
-    }
-  }
-  if (dt == F16) {
-    switch (v) {
-      case 0: return launch_sk<f16, 64, 64>(a, s);
-      case 1: return launch_sk<f16, 64, 32>(a, s);
-      default: return launch_sk<f16, 32, 32>(a, s);
-    }
-  }
-  switch (v) {
-    case 0: return launch_sk<bf16, 64, 64>(a, s);
-    case 1: return launch_sk<bf16, 64, 32>(a, s);
-    default: return launch_sk<bf16, 32, 32>(a, s);
-  }
-}
+hipError_t launch_conv_gemm_sk(int dt, const ConvGemmArgs &a, int tile, hipStream_t s) { return SF_DISPATCH_T(dt, launch_sk_tile<T>(a, tile, s)); }
 
 }  // namespace sf

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256) void conv_gemm_v2_kernel(const ConvGemmArgs a,
   }
 }
 
-template <typename T, int BM, int BN, int GEOM, bool CAT, int NSET> hipError_t launch_v2_n(const ConvGemmArgs &a, const V2Plan &pl, hipStream_t s) {
+template <typename T, int BM, int BN, int GEOM, bool CAT, int NSET> hipError_t launch_v2_n(const ConvGemmArgs &a, hipStream_t s) {
   constexpr int LD = BK + 16 / (int)sizeof(T);
   constexpr size_t stage_bytes = (size_t)(NSET == 1 ? 1 : 2) * (BM + BN) * LD * sizeof(T);
   constexpr size_t red_bytes = (size_t)BM * (BN + 4) * sizeof(float) + 16;
@@ -347,20 +347,28 @@ template <typename T, int BM, int BN, int GEOM, bool CAT, int NSET> hipError_t l
 // many workgroups a CU holds to overlap each other's loads: 54-92 registers instead of 88-192 give 7 / 4 / 3 workgroups per CU
 // for the 64x64 / 128x64 / 128x128 tiles and +15-45 % on every MFMA-bound shape (tools/gemm_big.py); two or four chunks in
 // flight per workgroup measured the same or slower.  fp32 (parity path) keeps the double-buffered form.
-template <typename T, int BM, int BN, int GEOM, bool CAT> hipError_t launch_v2_t(const ConvGemmArgs &a, const V2Plan &pl, hipStream_t s) {
-  if constexpr (sizeof(T) == 2) return launch_v2_n<T, BM, BN, GEOM, CAT, 1>(a, pl, s);
-  else return launch_v2_n<T, BM, BN, GEOM, CAT, 2>(a, pl, s);
+template <typename T, int BM, int BN, int GEOM, bool CAT> hipError_t launch_v2_t(const ConvGemmArgs &a, hipStream_t s) {
+  if constexpr (sizeof(T) == 2) return launch_v2_n<T, BM, BN, GEOM, CAT, 1>(a, s);
+  else return launch_v2_n<T, BM, BN, GEOM, CAT, 2>(a, s);
 }
 
-template <typename T, int BM, int BN> hipError_t launch_v2_g(const ConvGemmArgs &a, const V2Plan &pl, hipStream_t s) {
-  if (a.geom == 1) return a.cin2 ? hipErrorInvalidValue : launch_v2_t<T, BM, BN, 1, false>(a, pl, s);
-  return a.cin2 ? launch_v2_t<T, BM, BN, 0, true>(a, pl, s) : launch_v2_t<T, BM, BN, 0, false>(a, pl, s);
+template <typename T, int BM, int BN> hipError_t launch_v2_g(const ConvGemmArgs &a, hipStream_t s) {
+  if (a.geom == 1) return a.cin2 ? hipErrorInvalidValue : launch_v2_t<T, BM, BN, 1, false>(a, s);
+  return a.cin2 ? launch_v2_t<T, BM, BN, 0, true>(a, s) : launch_v2_t<T, BM, BN, 0, false>(a, s);
+}
+
+template <typename T> hipError_t launch_v2(const ConvGemmArgs &a, int tile, hipStream_t s) {
+  switch (tile) {
+    case 0: return launch_v2_g<T, 128, 128>(a, s);
+    case 1: return launch_v2_g<T, 128, 64>(a, s);
+    default: return launch_v2_g<T, 64, 64>(a, s);
+  }
 }
 
 }  // namespace
 
-// eligibility + tile choice
-bool conv_gemm_v2_plan(int dt, const ConvGemmArgs &a, V2Plan &pl) {
+// eligibility + tile choice (0: 128x128, 1: 128x64, 2: 64x64)
+bool conv_gemm_v2_plan(int dt, const ConvGemmArgs &a, int &tile) {
   if (a.pro != 0 || (a.cin % BK) || (a.cin2 % 32) || (a.K % 32) || a.n_store % 4) return false;
   if (a.geom == 1 && a.cin2) return false;
   const size_t es = dsize(dt), lim = 0x7FFFFFF0ull;
@@ -370,42 +378,16 @@ bool conv_gemm_v2_plan(int dt, const ConvGemmArgs &a, V2Plan &pl) {
   if (bA >= lim || (size_t)a.M * (a.src2_ld > 0 ? a.src2_ld : 1) * es >= lim || (size_t)a.N * a.K * es >= lim) return false;
   auto tiles = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.n_store + bn - 1) / bn); };
   // Measured on MI355X (tools/gemm_sweep.py, bf16): 128x128 wins once it yields >= ~300 workgroups, 64x64 otherwise;
-  // below ~500 64x64-tiles the wave-split-K kernel with 32x32 tiles is faster (see launch_conv_gemm).
+  // below ~500 64x64-tiles the wave-split-K kernel with 32x32 tiles is faster (see conv_gemm_plan).
   // 64x64 wins almost everywhere once seven workgroups fit a CU; 128x64 where few row tiles meet wide outputs and a long K
   // (deep U-Net levels at the guidance batch); fp32 keeps the old rule (two-buffer form, parity path only)
-  if (dt == F32) pl.variant = (a.n_store >= 128 && tiles(128, 128) >= 300) ? 0 : 2;
-  else pl.variant = (a.M <= 8192 && a.n_store >= 1024 && a.K >= 2048) ? 1 : 2;
+  if (dt == F32) tile = (a.n_store >= 128 && tiles(128, 128) >= 300) ? 0 : 2;
+  else tile = (a.M <= 8192 && a.n_store >= 1024 && a.K >= 2048) ? 1 : 2;
   const ConvGemmForce &f = g_conv_gemm_force;
-  if (f.path == 4 && f.tile >= 0 && f.tile <= 2) pl.variant = f.tile;
+  if (f.path == 4 && f.tile >= 0 && f.tile <= 2) tile = f.tile;
   return true;
 }
 
-const char *conv_gemm_v2_name(int dt, const V2Plan &pl) {
-  static const char *n[2][3] = {{"conv_gemm_v2<f32,128x128>", "conv_gemm_v2<f32,128x64>", "conv_gemm_v2<f32,64x64>"},
-                                {"conv_gemm_v2<bf16,128x128>", "conv_gemm_v2<bf16,128x64>", "conv_gemm_v2<bf16,64x64>"}};
-  return label_for_dtype(dt, n[dt == F32 ? 0 : 1][pl.variant]);
-}
-
-hipError_t launch_conv_gemm_v2(int dt, const ConvGemmArgs &a, const V2Plan &pl, hipStream_t s) {
-  if (dt == F32) {
-    switch (pl.variant) {
-      case 0: return launch_v2_g<float, 128, 128>(a, pl, s);
-      case 1: return launch_v2_g<float, 128, 64>(a, pl, s);
-      default: return launch_v2_g<float, 64, 64>(a, pl, s);
-    }
-  }
-  if (dt == F16) {
-    switch (pl.variant) {
-      case 0: return launch_v2_g<f16, 128, 128>(a, pl, s);
-      case 1: return launch_v2_g<f16, 128, 64>(a, pl, s);
-      default: return launch_v2_g<f16, 64, 64>(a, pl, s);
-    }
-  }
-  switch (pl.variant) {
-    case 0: return launch_v2_g<bf16, 128, 128>(a, pl, s);
-    case 1: return launch_v2_g<bf16, 128, 64>(a, pl, s);
-    default: return launch_v2_g<bf16, 64, 64>(a, pl, s);
-  }
-}
+hipError_t launch_conv_gemm_v2(int dt, const ConvGemmArgs &a, int tile, hipStream_t s) { return SF_DISPATCH_T(dt, launch_v2<T>(a, tile, s)); }
 
 }  // namespace sf

@@ -440,8 +440,20 @@ template <typename T, int BM, int BN, bool CAT, int NSET, int X3 = 0> hipError_t
 }
 
 // two chunks in flight per wave: three or four measured slower (register pressure against 2.7 waves per SIMD)
-template <typename T, int BM, int BN, bool CAT> hipError_t launch_wp2(const ConvGemmArgs &a, hipStream_t s) {
-  return launch_wp3<T, BM, BN, CAT, 2>(a, s);
+template <typename T, int BM, int BN, int X3 = 0> hipError_t launch_wp_cat(const ConvGemmArgs &a, hipStream_t s) {
+  return a.cin2 ? launch_wp3<T, BM, BN, true, 2, X3>(a, s) : launch_wp3<T, BM, BN, false, 2, X3>(a, s);
+}
+// tile: 0 = 64x64, 1 = 64x32, 2 = 32x32; split mode (fp32 launches only): 32x32 tiles (the variants the fp32 engine uses on short activations)
+template <typename T> hipError_t launch_wp(const ConvGemmArgs &a, int tile, int split, hipStream_t s) {
+  if constexpr (sizeof(T) == 4) {
+    if (split == X3_BF16) return launch_wp3<T, 32, 32, false, 2, X3_BF16>(a, s);   // gradients: one source
+    if (split == X3_F16) return launch_wp_cat<T, 32, 32, X3_F16>(a, s);
+  }
+  switch (tile) {
+    case 0: return launch_wp_cat<T, 64, 64>(a, s);
+    case 1: return launch_wp_cat<T, 64, 32>(a, s);
+    default: return launch_wp_cat<T, 32, 32>(a, s);
+  }
 }
 
 }  // namespace
@@ -456,33 +468,6 @@ bool conv_gemm_wp_ok(int dt, const ConvGemmArgs &a) {
   return true;
 }
 
-// variant: 0 = 64x64, 1 = 64x32, 2 = 32x32
-hipError_t launch_conv_gemm_wp(int dt, const ConvGemmArgs &a, int variant, hipStream_t s) {
-#define SF_WP(T, BM, BN) (a.cin2 ? launch_wp2<T, BM, BN, true>(a, s) : launch_wp2<T, BM, BN, false>(a, s))
-  if (dt == F32 && a.wx) {   // split mode: 32x32 tiles (the variants the fp32 engine uses on short activations)
-    if (a.wx_mode == X3_BF16) return a.cin2 ? hipErrorInvalidValue : launch_wp3<float, 32, 32, false, 2, X3_BF16>(a, s);
-    return a.cin2 ? launch_wp3<float, 32, 32, true, 2, X3_F16>(a, s) : launch_wp3<float, 32, 32, false, 2, X3_F16>(a, s);
-  }
-  if (dt == F32) {
-    switch (variant) {
-      case 0: return SF_WP(float, 64, 64);
-      case 1: return SF_WP(float, 64, 32);
-      default: return SF_WP(float, 32, 32);
-    }
-  }
-  if (dt == F16) {
-    switch (variant) {
-      case 0: return SF_WP(f16, 64, 64);
-      case 1: return SF_WP(f16, 64, 32);
-      default: return SF_WP(f16, 32, 32);
-    }
-  }
-  switch (variant) {
-    case 0: return SF_WP(bf16, 64, 64);
-    case 1: return SF_WP(bf16, 64, 32);
-    default: return SF_WP(bf16, 32, 32);
-  }
-#undef SF_WP
-}
+hipError_t launch_conv_gemm_wp(int dt, const ConvGemmArgs &a, int tile, int split, hipStream_t s) { return SF_DISPATCH_T(dt, launch_wp<T>(a, tile, split, s)); }
 
 }  // namespace sf

@@ -111,53 +111,75 @@ struct ConvGemmArgs {
   // so that the kernels stay parity-tested.  An explicit argument: no process-wide switch for the dispatch to disagree with itself about.
   int mt_ln = 0;
 };
-struct V2Plan {
-  int variant = 2;  // 0: 128x128, 1: 128x64, 2: 64x64
+// ---------------------------------------------------------------------------------------
+// The dispatcher (conv_gemm.hip).  Which kernel family and tile a launch takes is decided ONCE, by conv_gemm_plan (launch_conv_gemm) or
+// conv_gemm_ln_plan (launch_conv_gemm_ln); the launch, the profiling label and every query below are reads of that plan.
+// ---------------------------------------------------------------------------------------
+enum ConvGemmFamily { CG_INVALID = 0, CG_CLASSIC, CG_V2, CG_SK, CG_FAST, CG_WP, CG_RS, CG_MT };
+struct ConvGemmPlan {
+  int family = CG_INVALID;   // CG_INVALID: no kernel takes the arguments (the launch returns hipErrorInvalidValue)
+  int tile = 0;              // the family's own tile variant (the tables beside each family's launcher)
+  int split = 0;             // 0, X3_F16, X3_BF16: the kernel multiplies the split image (wx / wfrx) and never reads ConvGemmArgs::w
+  bool ln = false;           // consumer-side row LayerNorm (conv_gemm_ln_plan)
+  bool wide = false;         // conv_gemm_fast: 256-wide K chunks (ConvGemmForce::sk == 64)
+  // the launch honours ConvGemmArgs::rowpart_out / gnpart_out / src_x3 (and arming them does not move it to another family)
+  bool rowpart = false, gnpart = false, src_x3 = false;
+  const char *label = "conv_gemm<invalid>";   // profiling / test key
 };
-bool conv_gemm_v2_plan(int dt, const ConvGemmArgs &a, V2Plan &pl);
-const char *conv_gemm_v2_name(int dt, const V2Plan &pl);
-hipError_t launch_conv_gemm_v2(int dt, const ConvGemmArgs &a, const V2Plan &pl, hipStream_t s);
-hipError_t launch_conv_gemm(int dt, const ConvGemmArgs &a, hipStream_t s);
-// macro-tile kernel (conv_gemm_mt.hip): 256x128 tiles, LDS-DMA ring; 16-bit types, long activations
-bool conv_gemm_mt_ok(int dt, const ConvGemmArgs &a);
-bool conv_gemm_prefers_mt(const ConvGemmArgs &a);
-bool conv_gemm_mt_wanted(int dt, const ConvGemmArgs &a);   // eligible AND preferred (the fp32 rule differs: conv_gemm_mt.hip)
-// true when launch_conv_gemm(F32, a) would run on a kernel that can read its first source pre-split (ConvGemmArgs::src_x3)
-bool conv_gemm_src_x3_ok(const ConvGemmArgs &a);
-hipError_t launch_conv_gemm_mt(int dt, const ConvGemmArgs &a, hipStream_t s);
-const char *conv_gemm_mt_name(const ConvGemmArgs &a);   // label of the tile variant it picks (bf16 spelling)
-// true when launch_conv_gemm would run `a` on a kernel that honours rowpart_out (fast / wp, 32x32 tiles; macro tiles with SF_MT_LN=1)
-bool conv_gemm_emits_rowpart(int dt, const ConvGemmArgs &a);
+ConvGemmPlan conv_gemm_plan(int dt, const ConvGemmArgs &a);      // what launch_conv_gemm runs
+ConvGemmPlan conv_gemm_ln_plan(int dt, const ConvGemmArgs &a);   // what launch_conv_gemm_ln runs: a GEMM whose first source is LayerNorm-
+                                                                 // modulated on the fly from producer-side row partials (see ConvGemmArgs)
+hipError_t launch_conv_gemm_planned(int dt, const ConvGemmArgs &a, const ConvGemmPlan &p, hipStream_t s);
+hipError_t launch_conv_gemm(int dt, const ConvGemmArgs &a, hipStream_t s);      // = plan + launch_conv_gemm_planned
+hipError_t launch_conv_gemm_ln(int dt, const ConvGemmArgs &a, hipStream_t s);
+// queries: callers ask BEFORE they set rowpart_out / gnpart_out / src_x3 / wx (the query arms its copy of the arguments)
+bool conv_gemm_emits_rowpart(int dt, const ConvGemmArgs &a);      // the launch would write the row partials (ConvGemmArgs::rowpart_out)
+bool conv_gemm_emits_gnpart(int dt, const ConvGemmArgs &a);       // ... the GroupNorm tile statistics (gnpart_out)
+bool conv_gemm_src_x3_ok(const ConvGemmArgs &a);                  // launch_conv_gemm(F32, a) can read its first source pre-split (src_x3)
+bool conv_gemm_reads_split_only(int dt, const ConvGemmArgs &a);   // with a split image at hand (wx), is ConvGemmArgs::w never read?
+bool conv_gemm_ln_ok(int dt, const ConvGemmArgs &a);                          // conv_gemm_ln_plan(dt, a).family != CG_INVALID
+const char *conv_gemm_variant_name(int dt, const ConvGemmArgs &a);            // conv_gemm_plan(dt, a).label
+const char *conv_gemm_ln_variant_name(int dt, const ConvGemmArgs &a);         // conv_gemm_ln_plan(dt, a).label
+// a guess from rows and N alone (no arguments exist yet): few enough 32x32 tiles for the small-batch kernels -- which weight image to prefetch
+bool conv_gemm_rs_rows_ok(int64_t rows, int N);
+// bytes of dynamic LDS the GN table needs is bounded; returns false when the shape is unsupported.
+bool conv_gemm_supported(int dt, const ConvGemmArgs &a);
+// the label of the bf16 build with the type renamed when dt == F16 (interned string)
+const char *label_for_dtype(int dt, const char *bf16_label);
+// Tuning hook (sf_bench_conv1d only; not thread-safe): force the kernel family / tile of launch_conv_gemm.
+//   path: 0 automatic, 1 classic (conv_gemm), 2 wave-split-K (sk / fast), 4 v2, 5 wave-private (wp), 6 macro tiles;
+//   tile: -1 automatic else variant index;
+//   sk: reserved (was the grid split-K factor of v2; 64 selects the 256-wide chunk variant of conv_gemm_fast).
+struct ConvGemmForce {
+  int path = 0, tile = -1, sk = -1;
+};
+extern ConvGemmForce g_conv_gemm_force;
+// Per-family rules, each beside its kernel; called by the two plan functions only.  *_ok: what the kernel implements; *_prefers: the
+// measured thresholds; *_tile: the family's tile variant; the launchers take the plan's tile / split and choose nothing.
+bool conv_gemm_v2_plan(int dt, const ConvGemmArgs &a, int &tile);   // eligibility + tile: 0 = 128x128, 1 = 128x64, 2 = 64x64
+hipError_t launch_conv_gemm_v2(int dt, const ConvGemmArgs &a, int tile, hipStream_t s);
+int conv_gemm_sk_variant(const ConvGemmArgs &a);                    // sk / fast / wp tile: 0 = 64x64, 1 = 64x32, 2 = 32x32
+hipError_t launch_conv_gemm_sk(int dt, const ConvGemmArgs &a, int tile, hipStream_t s);
+bool conv_gemm_fast_ok(int dt, const ConvGemmArgs &a);
+hipError_t launch_conv_gemm_fast(int dt, const ConvGemmArgs &a, const ConvGemmPlan &p, hipStream_t s);   // tile, split, ln, wide
+bool conv_gemm_wp_ok(int dt, const ConvGemmArgs &a);
+bool conv_gemm_prefers_wp(const ConvGemmArgs &a);
+hipError_t launch_conv_gemm_wp(int dt, const ConvGemmArgs &a, int tile, int split, hipStream_t s);
 // register-staged kernel (conv_gemm_rs.hip): 32x32 tiles, all operand fragments of a wave in flight, fragment-ordered weights
 bool conv_gemm_rs_ok(int dt, const ConvGemmArgs &a);
-bool conv_gemm_rs_rows_ok(int64_t rows, int N);   // few enough 32x32 tiles for the small-batch kernels (the rule launch_conv_gemm applies)
 hipError_t launch_conv_gemm_rs(int dt, const ConvGemmArgs &a, hipStream_t s);
+// macro-tile kernel (conv_gemm_mt.hip): 256x128 tiles, LDS-DMA ring; long activations
+bool conv_gemm_mt_ok(int dt, const ConvGemmArgs &a);
+bool conv_gemm_mt_prefers(int dt, const ConvGemmArgs &a);   // the rule differs between the 16-bit types, fp32 and fp32 with a split image
+int conv_gemm_mt_tile(int dt, const ConvGemmArgs &a);
+constexpr int CG_MT_TILES = 11;
+hipError_t launch_conv_gemm_mt(int dt, const ConvGemmArgs &a, int tile, int split, hipStream_t s);
 hipError_t launch_pack_wfr(int dt, const void *w /* [N][K], compute type */, int N, int K, void *out, hipStream_t s);
 hipError_t launch_pack_wfrx(const float *w /* [N][K] fp32 */, int N, int K, void *out, hipStream_t s);   // split fragment order (ConvGemmArgs::wfrx)
 // split-fp16 image of a packed fp32 [N][K] matrix (K % 32 == 0): out[n][k / 32][0][k % 32] = hi, [1][k % 32] = lo' (common.h, x3_split)
 hipError_t launch_pack_wx(const float *w, int N, int K, void *out, hipStream_t s, int mode = 1);
 // Conv1d weight (N, C, taps) fp32 -> out[n][tap * C + c] fp32 and the split image of the same matrix, one pass ((taps * C) % 32 == 0)
 hipError_t launch_pack_conv_x(const float *w, int N, int C, int taps, float *out, void *outx, int mode, hipStream_t s);
-// true when launch_conv_gemm would run `a` on the kernel that honours gnpart_out (wp, 32x32 tiles)
-bool conv_gemm_emits_gnpart(int dt, const ConvGemmArgs &a);
-// GEMM whose first source is LayerNorm-modulated on the fly from producer-side row partials (see ConvGemmArgs)
-bool conv_gemm_ln_ok(int dt, const ConvGemmArgs &a);
-hipError_t launch_conv_gemm_ln(int dt, const ConvGemmArgs &a, hipStream_t s);
-const char *conv_gemm_ln_variant_name(int dt, const ConvGemmArgs &a);
-// Tuning hook (sf_bench_conv1d only; not thread-safe): force the kernel family / tile of launch_conv_gemm.
-//   path: 0 automatic, 1 classic (conv_gemm), 2 wave-split-K (sk / fast), 4 v2;  tile: -1 automatic else variant index;
-//   sk: reserved (was the grid split-K factor of v2; 64 selects the 256-wide chunk variant of conv_gemm_fast).
-struct ConvGemmForce {
-  int path = 0, tile = -1, sk = -1;
-};
-extern ConvGemmForce g_conv_gemm_force;
-// name of the tile variant launch_conv_gemm picks for these arguments (profiling labels)
-const char *conv_gemm_variant_name(int dt, const ConvGemmArgs &a);
-bool conv_gemm_reads_split_only(int dt, const ConvGemmArgs &a);   // with ConvGemmArgs::wx at hand, is ConvGemmArgs::w never read? (conv_gemm.hip)
-// the label of the bf16 build with the type renamed when dt == F16 (interned string)
-const char *label_for_dtype(int dt, const char *bf16_label);
-// bytes of dynamic LDS the GN table needs is bounded; returns false when the shape is unsupported.
-bool conv_gemm_supported(int dt, const ConvGemmArgs &a);
 
 // ---------------------------------------------------------------------------------------
 // Thin-level convolution (conv_thin.hip): <= 64 output channels on long sequences, one workgroup per `rw` consecutive

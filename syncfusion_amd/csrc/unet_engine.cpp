@@ -892,9 +892,8 @@ struct Exec {
       }();
       if (touch > 0 && !u.prof_on) SF_HIP(launch_touch(w.w, (size_t)w.N * w.K * dsize(u.dt), touch, reinterpret_cast<unsigned *>(p.step + 8), s));
       if (dt_in != u.dt || (dt_out != u.dt && !a.out_f32)) fail(SF_ERR_INVALID, "internal: dtype mismatch on the MFMA path");
-      if (ln) timed(conv_gemm_ln_variant_name(u.dt, a), flops + 8.0 * a.M * a.cin, bytes,
-                    [&] { SF_HIP(launch_conv_gemm_ln(u.dt, a, s)); });
-      else timed(conv_gemm_variant_name(u.dt, a), flops, bytes, [&] { SF_HIP(launch_conv_gemm(u.dt, a, s)); });
+      const ConvGemmPlan pl = ln ? conv_gemm_ln_plan(u.dt, a) : conv_gemm_plan(u.dt, a);   // decided once: the label and the launch read it
+      timed(pl.label, flops + (ln ? 8.0 * a.M * a.cin : 0.0), bytes, [&] { SF_HIP(launch_conv_gemm_planned(u.dt, a, pl, s)); });
     }
   }
 
