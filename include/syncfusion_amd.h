@@ -515,6 +515,22 @@ int sf_op_onset_bce_fwd(const float *z, const float *t, int64_t n, float *loss, 
 int sf_op_onset_bce_bwd(const float *z, const float *t, const float *stats, const float *g, int64_t n, float *dz, void *stream);
 int sf_op_onset_metrics(const float *z, const float *t, int N, int T, float threshold, double *out, void *ws, int64_t ws_bytes, void *stream);
 
+/* The device step of the onset net's test stage (main/module_onset.py:99-125 test_step, :142-183 log_annotations) for one batch of (N, T)
+ * fp32 logits and fp32 0 / 1 labels, from device memory to device memory: nothing is read back, nothing synchronises.
+ *   rows   table row r = clip0 + n of clip n: pred_frames[r, 0 .. pred_count[r]) = the frames t with logits[n, t] > logit_threshold in
+ *          ascending order (the reference thresholds the RAW logit at 0.5, :160-162; a NaN logit is no onset), the rest of the row -1;
+ *          target_count / target_frames the same for labels[n, t] != 0 (np.nonzero).  Tables: (capacity) and (capacity, T) int32; rows
+ *          outside [clip0, clip0 + N) are not touched.  A clip's rows depend on that clip only.
+ *   sums   sums[5] (fp64) += (N loss, N AP, N Acc, N OnsNumAcc, N): loss as sf_op_onset_bce_fwd, the metrics as sf_op_onset_metrics at
+ *          metric_threshold (0.75, on the sigmoid) give them for this batch, bit for bit; one thread adds in this order, NaN and inf
+ *          propagate (a one-class batch: NaN AP / Acc).  sums[k] / sums[4] is the epoch mean weighted by batch size.
+ * N * T <= 2^24 (SF_ERR_UNSUPPORTED above), clip0 + N <= capacity (SF_ERR_SHAPE), ws and sums 8-byte aligned,
+ * ws_bytes >= sf_op_onset_test_workspace_bytes(N, T) (-1 for N < 1, T < 1 or N * T > 2^24). */
+int64_t sf_op_onset_test_workspace_bytes(int N, int T);
+int sf_op_onset_test_step(const float *logits, const float *labels, int N, int T, float logit_threshold, float metric_threshold, int64_t clip0,
+                          int64_t capacity, int32_t *pred_count, int32_t *pred_frames, int32_t *target_count, int32_t *target_frames,
+                          double *sums, void *ws, int64_t ws_bytes, void *stream);
+
 /* The optimizer stage of a training step: clip-by-global-norm and the AdamW update of EVERY listed tensor in three launches (two without
  * clipping).  Replaces torch.nn.utils.clip_grad_norm_ (a per-tensor norm pass and a read-modify-write scaling pass over the gradients)
  * followed by torch.optim.AdamW(fused=True).step() (exp/train_diffusion_gh.yaml:91-92 gradient_clip_val, main/module_diffusion.py:53-62 and

@@ -6,17 +6,18 @@ Public surface = the reference's own: ``DiffusionModel`` 
 runs in ``lib/libsyncfusion_amd.so`` (hand-written HIP, C ABI in include/syncfusion_amd.h).
 """
 from . import _lib  # noqa: F401
-from . import audio_features, autograd, evaluation, fad, frame_transforms, onset_training, shards, training, video_chunks  # noqa: F401
+from . import audio_features, autograd, evaluation, fad, frame_transforms, onset_test, onset_training, shards, training, video_chunks  # noqa: F401
 from .config import instantiate, instantiate_class, instantiate_frames_transforms, instantiate_model_yaml
 from .diffusion import DiffusionModel, LinearSchedule, UNetV0, VDiffusion, VSampler
 from .audio_features import MelSpectrogram, mel_filterbank, onset_detect, onset_strength
 from .encoder1d import Encoder1d
 from .evaluation import evaluate_onsets
 from .fad import VGGish, VGGishConfig, embedding_statistics, evaluate_fad, frechet_distance
-from .generation import generate_batch, generate_dataset
+from .generation import generate_batch, generate_dataset, prepare_gt_for_fad
 from .module import Model, RandomEmbedder
 from .module_onset import Model as OnsetModel
 from .onset_net import VideoOnsetNet
+from .onset_test import OnsetTestStage, annotation_rows, pack_onset_preds, test_onset_model
 from .onset_training import GraphedOnsetTrainStep
 from .onset_glue import cut_prefix_crop, onsets_to_track
 from .resample import resample
@@ -26,5 +27,6 @@ __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule
            "GraphedOnsetTrainStep",           "RandomEmbedder", "generate_batch", "generate_dataset", "instantiate", "instantiate_model_yaml", "onsets_to_track", "cut_prefix_crop", "resample",
            "allreduce_gradients", "frame_transforms", "instantiate_class", "instantiate_frames_transforms",
            "audio_features", "evaluation", "MelSpectrogram", "mel_filterbank", "onset_detect", "onset_strength", "evaluate_onsets",
-           "fad", "VGGish", "VGGishConfig", "embedding_statistics", "frechet_distance", "evaluate_fad"]
+           "fad", "VGGish", "VGGishConfig", "embedding_statistics", "frechet_distance", "evaluate_fad",
+           "onset_test", "OnsetTestStage", "annotation_rows", "pack_onset_preds", "test_onset_model", "prepare_gt_for_fad"]
 __version__ = "0.1.0"

@@ -175,6 +175,11 @@ SYMBOLS = {
     "sf_op_onset_bce_bwd": (_I, [_P, _P, _P, _P, _L, _P, _P]),
     # (z, t, N, T, threshold, out, ws, ws_bytes, stream)
     "sf_op_onset_metrics": (_I, [_P, _P, _I, _I, _F, _P, _P, _L, _P]),
+    # the device step of the onset test stage (syncfusion_amd/onset_test.py)
+    "sf_op_onset_test_workspace_bytes": (_L, [_I, _I]),
+    # (logits, labels, N, T, logit_threshold, metric_threshold, clip0, capacity, pred_count, pred_frames, target_count, target_frames, sums,
+    #  ws, ws_bytes, stream)
+    "sf_op_onset_test_step": (_I, [_P, _P, _I, _I, _F, _F, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
     # the optimizer stage: clip-by-global-norm + AdamW over one device descriptor table (syncfusion_amd/optim.py)
     "sf_optim_workspace_bytes": (_L, [_I]),
     # (desc_dev, n_tensors, total_chunks, hyper_dev, n_groups, clip, result_dev, ws, ws_bytes, stream)

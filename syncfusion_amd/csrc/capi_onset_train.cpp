@@ -1,6 +1,6 @@
 // VideoOnsetNet training: the op-level C-ABI entry points behind syncfusion_amd/onset_training.py (fp32; the reference trains the onset net in
 // fp32: cfg/trainer/trainer-onset*.yaml sets no precision).  Kernels: onset_train.hip, plus the implicit-GEMM forward (launch_conv_gemm, geom 1);
-// onset_loss.hip for the loss and the step metrics behind syncfusion_amd/onset_loss.py.
+// onset_loss.hip for the loss and the step metrics behind syncfusion_amd/onset_loss.py; onset_test.hip for the test stage (onset_test.py).
 #include <algorithm>
 #include <exception>
 
@@ -273,6 +273,28 @@ int sf_op_onset_metrics(const float *z, const float *t, int N, int T, float thre
   const int64_t need = onset_loss_ws_bytes(n);
   if (ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
   SF_HIP(launch_onset_metrics(z, t, N, T, threshold, out, ws, static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int64_t sf_op_onset_test_workspace_bytes(int N, int T) {
+  if (N < 1 || T < 1 || (int64_t)N * T > ONSET_METRICS_MAX) return -1;
+  return onset_test_ws_bytes(N, T);
+}
+
+int sf_op_onset_test_step(const float *logits, const float *labels, int N, int T, float logit_threshold, float metric_threshold, int64_t clip0,
+                          int64_t capacity, int32_t *pred_count, int32_t *pred_frames, int32_t *target_count, int32_t *target_frames,
+                          double *sums, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!logits || !labels || !pred_count || !pred_frames || !target_count || !target_frames || !sums || !ws) fail(SF_ERR_INVALID, "null argument");
+  if (N < 1 || T < 1 || clip0 < 0) fail(SF_ERR_INVALID, "N >= 1, T >= 1 and clip0 >= 0 required");
+  if (clip0 > capacity || (int64_t)N > capacity - clip0) fail(SF_ERR_SHAPE, "rows [clip0, clip0 + N) do not fit the tables' capacity");
+  if ((int64_t)N * T > ONSET_METRICS_MAX) fail(SF_ERR_UNSUPPORTED, "the test step takes at most 2^24 logits (the step metrics' limit)");
+  if (((uintptr_t)ws | (uintptr_t)sums) & 7u) fail(SF_ERR_INVALID, "misaligned workspace or sums");
+  const int64_t need = onset_test_ws_bytes(N, T);
+  if (ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  SF_HIP(launch_onset_test_step(logits, labels, N, T, logit_threshold, metric_threshold, clip0, pred_count, pred_frames, target_count,
+                                target_frames, sums, ws, static_cast<hipStream_t>(stream)));
   return SF_OK;
   SF_API_END
 }

@@ -579,6 +579,17 @@ hipError_t launch_onset_bce_bwd(const float *z, const float *t, const float *sta
 // out[3] (fp64) = AP, Acc, OnsNumAcc of the (N, T) logits z and 0 / 1 labels t
 hipError_t launch_onset_metrics(const float *z, const float *t, int N, int T, float threshold, double *out, void *ws, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// Device step of the onset TEST stage (onset_test.hip; main/module_onset.py:99-125, 142-183): the thresholded frames of every clip
+// compacted into epoch table rows [clip0, clip0 + N) (one wave per clip, ballot prefix, -1 padding) and the batch's loss / metrics (the
+// launchers above) added into sums[5] = (N loss, N AP, N Acc, N OnsNumAcc, N), fp64, by one thread.  ws >= onset_test_ws_bytes(N, T),
+// 8-byte aligned.  The caller checks clip0 + N against the tables' capacity.
+// ---------------------------------------------------------------------------------------
+int64_t onset_test_ws_bytes(int N, int T);
+hipError_t launch_onset_test_step(const float *logits, const float *labels, int N, int T, float logit_threshold, float metric_threshold,
+                                  int64_t clip0, int32_t *pred_count, int32_t *pred_frames, int32_t *target_count, int32_t *target_frames,
+                                  double *sums, void *ws, hipStream_t s);
+
 // BatchNorm (eval) -> per-channel scale / shift
 hipError_t launch_bn_fold(const float *gamma, const float *beta, const float *mean, const float *var, float eps, int C,
                           float *scale, float *shift, hipStream_t s);

@@ -178,3 +178,48 @@ def generate_dataset(experiment_path: Union[str, Path], model, dataset: Iterable
                 written.append(experiment_path / f"{stem}_cond.wav")
             chunk_id += 1
     return written
+
+
+@torch.no_grad()
+def prepare_gt_for_fad(experiment_path: Union[str, Path], dataset: Iterable, batch_size: int = 16, num_workers: int = 4,
+                       sample_rate: int = 48000, one_chunk_per_track: bool = False, downsample_rate: Optional[int] = None) -> List[Path]:
+    """Same signature as main/dataset_diffusion.py:146-197: the ground-truth directory ``evaluate_fad`` takes as ``gt_path``.  The waveform
+    chunks of ``dataset`` (batched as ``generate_dataset`` batches them, ``iter_batches``) are written under the names ``generate_dataset``
+    gives the generated ones: ``{chunk_id}.wav`` with the same crude resume (a batch whose LAST file exists is skipped and counted), or,
+    with ``one_chunk_per_track``, ``{basename(filename)}.wav`` -- there the reference's "Skipping" only prints and the batch is written
+    again; so it is here.  ``downsample_rate``: the chunks go through this package's ``resample`` on the device (the reference resamples
+    clip by clip with torchaudio on the CPU) and the files carry that rate.  Files are written by ``save_wav``."""
+    experiment_path = Path(experiment_path)
+    experiment_path.mkdir(exist_ok=True, parents=True)
+    written: List[Path] = []
+    chunk_id = 0
+    for batch in iter_batches(dataset, batch_size, num_workers):
+        waveforms, _, _, _, filenames = batch
+        B = waveforms.shape[0]
+        if not one_chunk_per_track:
+            last = experiment_path / f"{chunk_id + B - 1}.wav"
+            if last.exists():                                                       # :166-173
+                print(f"Skipping path: {last}")
+                chunk_id += B
+                continue
+            print(f"{chunk_id=}")
+        else:
+            last = experiment_path / f"{str(filenames[-1]).split('/')[-1]}.wav"
+            if last.exists():                                                       # :175-179: prints, and goes on to write
+                print(f"Skipping path: {last}")
+            print(f"{filenames[0] = }")
+        out_sr = sample_rate
+        if downsample_rate:                                                         # :186-189, one device call for the batch
+            if not waveforms.is_cuda:
+                waveforms = waveforms.to("cuda")                                    # the resampler is a HIP kernel: no CPU path
+            waveforms = resample(waveforms, orig_freq=sample_rate, new_freq=downsample_rate)
+            out_sr = downsample_rate
+        for i in range(B):
+            if not one_chunk_per_track:
+                path = experiment_path / f"{chunk_id}.wav"
+                chunk_id += 1
+            else:
+                path = experiment_path / f"{str(filenames[i]).split('/')[-1]}.wav"
+            save_wav(path, waveforms[i], out_sr)
+            written.append(path)
+    return written

@@ -3,13 +3,18 @@
 Same constructor arguments and attribute (``model``: checkpoint keys ``model.net.model.*`` / ``model.fc.*``), the same AdamW set-up, the
 same ``common_step`` / ``training_step`` / ``validation_step`` / ``test_step`` returning the loss, and the same ``BCLoss`` (class-balanced
 ``BCEWithLogitsLoss``) with its ``evaluate`` metrics (AP, Acc, OnsNumAcc).  ``pytorch_lightning`` is the base class when it imports,
-otherwise the ``torch.nn.Module`` fallback of ``syncfusion_amd/module.py`` (``log`` is a no-op).  The wandb / CSV writers of the reference
-(``log_labels``, ``log_annotations``, ``concat_annotations``) are not mirrored; ``syncfusion_amd.onsets_to_track`` covers the logits -> onset
-times glue.
+otherwise the ``torch.nn.Module`` fallback of ``syncfusion_amd/module.py`` (``log`` is a no-op).
+
+The test stage (:99-129, 142-229: ``log_annotations`` per batch, ``concat_annotations`` at the end of the epoch) is
+``syncfusion_amd/onset_test.py``: ``Model(..., annotations_dir=DIR)`` makes ``test_step`` feed an ``OnsetTestStage`` with the logits
+``common_step`` computed (no second forward) whenever the batch carries ``video_name`` / ``start_frame`` / ``end_frame`` / ``frame_rate``,
+and ``on_test_epoch_end()`` finish it: ``DIR/media/annotations/{target,pred}/{video}.times.csv`` and ``test_results``.  With the default
+(``None``) ``test_step`` returns the loss and writes nothing, as before.  ``log_labels`` (wandb plots) is not mirrored;
+``syncfusion_amd.onsets_to_track`` is the in-memory, one-clip form of the logits -> onset times hand-off.
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -95,8 +100,11 @@ class Model(_Base):
     """Drop-in for ``main.module_onset.Model`` (cfg/model/model-onset.yaml ``class_path``)."""
 
     def __init__(self, lr: float, lr_beta1: float, lr_beta2: float, lr_eps: float, lr_weight_decay: float, onset_model: VideoOnsetNet,
-                 optimizer: str = "torch", loss: str = "torch"):
+                 optimizer: str = "torch", loss: str = "torch", annotations_dir: Optional[str] = None):
         super().__init__()
+        self.annotations_dir = annotations_dir
+        self.test_stage = None              # syncfusion_amd.onset_test.OnsetTestStage, created by the first annotated test batch
+        self.test_results: Optional[dict] = None
         self.optimizer = check_optimizer_choice(optimizer)
         self.loss_choice = check_loss_choice(loss)
         self.lr = lr
@@ -141,4 +149,21 @@ class Model(_Base):
         return self._step(batch, batch_idx, "val")
 
     def test_step(self, batch, batch_idx) -> Tensor:
-        return self._step(batch, batch_idx, "test")
+        if self.annotations_dir is None or "video_name" not in batch:
+            return self._step(batch, batch_idx, "test")
+        from .onset_test import OnsetTestStage, batch_chunks
+
+        frames, labels = batch["frames"], batch["label"]
+        pred = self.model(frames)                      # the one forward of the batch: loss, metrics and annotations read these logits
+        loss = self.loss(pred, labels)
+        self.log("loss/test", loss, on_step=False, on_epoch=True, prog_bar=True, logger=True, sync_dist=True)
+        self.log_metrics(self.loss.evaluate(pred, labels), mode="test")
+        if self.test_stage is None:
+            self.test_stage = OnsetTestStage(self, self.annotations_dir)
+        self.test_stage.step_logits(pred.detach(), labels, batch_chunks(batch))
+        return loss
+
+    def on_test_epoch_end(self) -> None:
+        """``concat_annotations`` (main/module_onset.py:127-128, 185-229): the merged files under ``annotations_dir`` and ``test_results``."""
+        if self.test_stage is not None:
+            self.test_results = self.test_stage.finish()
