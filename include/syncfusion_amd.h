@@ -408,6 +408,23 @@ int sf_op_resnet_mod_cbd(int dtype, const void *x, const float *w1, const float 
                          const float *gn1_b, const float *gn2_g, const float *gn2_b, int groups, float eps_gn, const float *scale_shift,
                          float eps_ln, int B, int L, int C, const float *w_inj, const float *b_inj, const void *ctx, int ctx_ld, int C2,
                          const float *badd, void *h_out, void *m_out, void *z_out, float *stats_out, void *ws, int64_t ws_bytes, void *stream);
+/* The item tail of the thin levels in one launch (conv_thin.hip, thin_tail: the second half of a ResnetItem, the ModulationItem and the
+ * InjectChannelsItem on the 8-, 32- and 64-channel levels), as the engine launches it behind the item's first convolution:
+ *   y = x + conv3(silu(groupnorm(h; gn)), w2) + b2;  m = layer_norm(y; eps_ln, no affine) * (1 + scale[b]) + shift[b];
+ *   z = m + Conv1x1(cat[m, ctx]) + b_inj (+ badd[b])
+ * h, x, z_out: (B, L, C) channels-last in `dtype`; ctx: (B, L, ctx_ld), its first C2 columns are read, of which c2_real carry weights
+ * (w_inj: (C, C + c2_real) fp32, zero-extended to C2 columns here; the engine pads its context rows to whole octets); w2: (C, C, 3) fp32;
+ * scale_shift: (B, 2C), required; badd: (B, C) or NULL.  The GroupNorm statistics of h are not computed here: stats_in is
+ * (B, nch_in, groups, 2) floats = (mean, M2) of h per chunk of chunk_in rows (the last chunk short) and group, as the producing
+ * convolution leaves them.  rw: positions per workgroup, a multiple of 32; 0 takes the engine's plan (*rw_out, optional, receives the
+ * value used).  stats_out (optional): (B, ceil(L / rw), groups, 2) = (mean, M2) of the stored z per workgroup and group.
+ * C / C2: 8 / 8, 32 / 32, 64 / 32 or 64 / 64 with 4 or 8 channels per group (one at C = 8); anything else, or an rw the kernel cannot
+ * stage, is SF_ERR_UNSUPPORTED before anything is launched. */
+int64_t sf_op_thin_tail_workspace_bytes(int dtype, int C, int C2);
+int sf_op_thin_tail(int dtype, const void *h, const void *x, const void *ctx, int ctx_ld, int c2_real, int C2, const float *stats_in, int nch_in,
+                    int chunk_in, const float *w2, const float *b2, const float *gn_g, const float *gn_b, int groups, float eps_gn,
+                    const float *scale_shift, float eps_ln, const float *w_inj, const float *b_inj, const float *badd, int B, int L, int C, int rw,
+                    void *z_out, float *stats_out, int *rw_out, void *ws, int64_t ws_bytes, void *stream);
 /* InjectChannels followed by the attention pre-norm projection, as the engine chains the two GEMMs of an item (a-unet InjectChannelsItem
  * + the LayerNorm / to_q | to_kv Linear of AttentionItem), 16-bit dtypes:
  *   z = m + Conv1x1(cat[m, ctx]) + b_inj            m:(B,L,C), ctx:(B,L,C2) channels-last in `dtype`; w_inj:(C, C + C2) fp32

@@ -141,6 +141,11 @@ SYMBOLS = {
     "sf_op_resnet_mod_cbd_workspace_bytes": (_L, [_I, _I, _I, _I]),
     "sf_op_resnet_mod_cbd": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _F, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P,
                                   _L, _P]),
+    "sf_op_thin_tail_workspace_bytes": (_L, [_I, _I, _I]),
+    # (dtype, h, x, ctx, ctx_ld, c2_real, C2, stats_in, nch_in, chunk_in, w2, b2, gn_g, gn_b, groups, eps_gn, scale_shift, eps_ln, w_inj, b_inj,
+    #  badd, B, L, C, rw, z_out, stats_out, rw_out, ws, ws_bytes, stream)
+    "sf_op_thin_tail": (_I, [_I, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _F, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P, _P,
+                             C.POINTER(C.c_int), _P, _L, _P]),
     "sf_bench_conv_cb": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float)]),
     "sf_op_ln_modulate": (_I, [_I, _P, _P, _F, _I, _I, _I, _P, _P]),
     "sf_op_attention": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),

@@ -685,6 +685,74 @@ int sf_op_resnet_mod_cbd(int dtype, const void *x, const float *w1, const float 
   SF_API_END
 }
 
+int64_t sf_op_thin_tail_workspace_bytes(int dtype, int C, int C2) {
+  if ((dtype != F32 && dtype != BF16 && dtype != F16) || C < 1 || C2 < 0) return -1;
+  Workspace dry(nullptr, 0);
+  dry.alloc((int64_t)C * 3 * C * (int64_t)dsize(dtype));      // conv2 weights, packed [C][3 C]
+  dry.alloc((int64_t)C * (C + C2) * (int64_t)dsize(dtype));   // InjectChannels weights, packed [C][C + C2]
+  return dry.used();
+}
+
+int sf_op_thin_tail(int dtype, const void *h, const void *x, const void *ctx, int ctx_ld, int c2_real, int C2, const float *stats_in, int nch_in,
+                    int chunk_in, const float *w2, const float *b2, const float *gn_g, const float *gn_b, int groups, float eps_gn,
+                    const float *scale_shift, float eps_ln, const float *w_inj, const float *b_inj, const float *badd, int B, int L, int C, int rw,
+                    void *z_out, float *stats_out, int *rw_out, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!h || !x || !stats_in || !w2 || !b2 || !gn_g || !gn_b || !scale_shift || !w_inj || !b_inj || !z_out || !ws) fail(SF_ERR_INVALID, "null argument");
+  if (dtype != F32 && dtype != BF16 && dtype != F16) fail(SF_ERR_UNSUPPORTED, "dtype: fp32, bf16 or fp16");
+  if (B < 1 || L < 1 || C < 8) fail(SF_ERR_INVALID, "bad shape");
+  if (C2 < 0 || C2 % 8 || c2_real < 0 || c2_real > C2 || (C2 > 0 && (!ctx || ctx_ld < C2 || ctx_ld % 8))) fail(SF_ERR_INVALID, "context operands inconsistent");
+  // the chunks of the input statistics tile the clip exactly: the last one is short, none is empty
+  if (nch_in < 1 || chunk_in < 1 || (int64_t)(nch_in - 1) * chunk_in >= L || (int64_t)nch_in * chunk_in < L)
+    fail(SF_ERR_INVALID, "nch_in chunks of chunk_in rows do not tile L = %d", L);
+  if (rw < 0 || rw % 32) fail(SF_ERR_UNSUPPORTED, "rw must be a multiple of 32 (0: the plan's choice)");
+  ThinTailArgs t;
+  if (rw == 0) rw = conv_thin_plan(B, L, C).rw;
+  t.rw = rw;
+  t.nchw = (L + rw - 1) / rw;
+  t.h = h;
+  t.x = x;
+  t.ctx = ctx;
+  t.ctx_ld = ctx_ld;
+  t.bias2 = b2;
+  t.bias3 = b_inj;
+  t.gamma = gn_g;
+  t.beta = gn_b;
+  t.stats_in = stats_in;
+  t.ss = scale_shift;
+  t.ss_ld = 2 * C;
+  t.badd = badd;
+  t.badd_ld = C;
+  t.out = z_out;
+  t.stats_out = stats_out;
+  t.B = B;
+  t.L = L;
+  t.C = C;
+  t.C2 = C2;
+  t.G = groups;
+  t.nch_in = nch_in;
+  t.chunk_in = chunk_in;
+  t.eps_gn = eps_gn;
+  t.eps_ln = eps_ln;
+  // every refusal comes before the first launch: a refused call writes nothing
+  if (groups < 1 || !thin_tail_supported(dtype, t)) fail(SF_ERR_UNSUPPORTED, "shape outside the thin-level tail's coverage (C / C2 = 8/8, 32/32, 64/32, 64/64; 4 or 8 channels per group)");
+  const int64_t need = sf_op_thin_tail_workspace_bytes(dtype, C, C2);
+  if (need < 0 || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  Workspace wk(ws, ws_bytes);
+  const int64_t es = (int64_t)dsize(dtype);
+  void *wp2 = wk.alloc((int64_t)C * 3 * C * es), *wp3 = wk.alloc((int64_t)C * (C + C2) * es);
+  t.w2 = wp2;
+  t.w3 = wp3;
+  SF_HIP(launch_pack_conv(dtype, w2, C, C, 0, C, 3, C, nullptr, wp2, 3 * C, 0, s));
+  SF_HIP(launch_pack_conv(dtype, w_inj, C, C + c2_real, 0, C, 1, C, nullptr, wp3, C + C2, 0, s));
+  if (C2) SF_HIP(launch_pack_conv(dtype, w_inj, C, C + c2_real, C, c2_real, 1, C2, nullptr, wp3, C + C2, C, s));
+  SF_HIP(launch_thin_tail(dtype, t, s));
+  if (rw_out) *rw_out = rw;
+  return SF_OK;
+  SF_API_END
+}
+
 int64_t sf_op_inject_prenorm_proj_workspace_bytes(int B, int L, int C, int C2, int N) {
   if (B < 1 || L < 1 || C < 32 || C2 < 0 || N < 8) return -1;
   const int64_t M = (int64_t)B * L, K1 = C + (C2 + 31) / 32 * 32;

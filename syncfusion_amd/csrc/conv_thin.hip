@@ -195,6 +195,78 @@ __device__ __forceinline__ float2 gn_merge_n(const float *__restrict__ sl, int G
   return make_float2(mu, rsqrtf(var + eps));
 }
 
+// The same merge for the groups of a workgroup with its global reads requested up front.  Half-wave hw of nhw takes groups
+// g0 + hw, g0 + hw + nhw, ...: NG of them per round, and of each the lane's first NP partials (j, j + 32, ...) plus gamma / beta of
+// the lane's channel are in registers before the first is used -- one memory round trip per round where a loop around gn_merge_n
+// pays one per partial and group.  Every address is clamped into its buffer (group < G, chunk < nch, channel of the group); what a
+// clamped lane read is never folded.  Partials beyond 32 NP of a group come from the loop as before (nch has no upper bound).
+// Fold order per lane and shuffle tree are gn_merge_n's.  The merge itself is welford_merge_t<true> with its products written as the
+// fused operations the compiler forms for it inside gn_merge_n's loop and tree: left to contraction, the unrolled context here came out
+// as other instructions (an unfused mean update) and the statistics differed in the last bit from the loop kernels'.
+__device__ __forceinline__ void welford_merge_fma(float &n, float &mean, float &m2, float nb, float mb, float m2b) {
+  if (nb <= 0.f) return;
+  const float tot = n + nb, r = __builtin_amdgcn_rcpf(tot);
+  const float delta = mb - mean;
+  mean = fmaf(nb * r, delta, mean);
+  m2 += fmaf(n * nb * r, delta * delta, m2b);
+  n = tot;
+}
+template <int NG, int NP> struct GnAhead {
+  float m[NG][NP], q[NG][NP], gam[NG], bet[NG];
+};
+template <int NG, int NP>
+__device__ __forceinline__ void gn_ahead_load(GnAhead<NG, NP> &p, const float *__restrict__ sb /* [nch][G][2] of the clip */,
+                                              const float *__restrict__ gamma, const float *__restrict__ beta, int G, int nch, int cpg, int g0,
+                                              int hw, int nhw, int lane32) {
+#pragma unroll
+  for (int gi = 0; gi < NG; ++gi) {
+    const int g = min(g0 + hw + gi * nhw, G - 1);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = min(lane32 + 32 * k, nch - 1);
+      p.m[gi][k] = sb[((size_t)i * G + g) * 2];
+      p.q[gi][k] = sb[((size_t)i * G + g) * 2 + 1];
+    }
+    const int c = g * cpg + min(lane32, cpg - 1);
+    p.gam[gi] = gamma[c];
+    p.bet[gi] = beta[c];
+  }
+}
+// -> sc[c] = rstd * gamma, sh[c] = beta - mean * rstd * gamma for the channels of the round's groups
+template <bool FAST, int NG, int NP>
+__device__ __forceinline__ void gn_ahead_fold(const GnAhead<NG, NP> &p, const float *__restrict__ sb, int G, int nch, int chunk_rows, int L,
+                                              int cpg, float eps, int g0, int hw, int nhw, int lane32, float *sc, float *sh) {
+  static_assert(FAST, "16-bit kernels: the reciprocal form of the merge");
+#pragma unroll
+  for (int gi = 0; gi < NG; ++gi) {
+    const int g = g0 + hw + gi * nhw;
+    if (g >= G) break;
+    float n = 0.f, mean = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = lane32 + 32 * k;
+      if (i < nch) welford_merge_fma(n, mean, m2, (float)min(chunk_rows, L - i * chunk_rows) * (float)cpg, p.m[gi][k], p.q[gi][k]);
+    }
+    for (int i = lane32 + 32 * NP; i < nch; i += 32) {
+      const int rows = min(chunk_rows, L - i * chunk_rows);
+      welford_merge_fma(n, mean, m2, (float)rows * (float)cpg, sb[((size_t)i * G + g) * 2], sb[((size_t)i * G + g) * 2 + 1]);
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {
+      const float nb = __shfl_down(n, off, 32), mb = __shfl_down(mean, off, 32), qb = __shfl_down(m2, off, 32);
+      welford_merge_fma(n, mean, m2, nb, mb, qb);
+    }
+    const float mu = __shfl(mean, 0, 32), var = div_t<FAST>(__shfl(m2, 0, 32), __shfl(n, 0, 32));
+    if (lane32 < cpg) {
+      const int c = g * cpg + lane32;
+      const float s = rsqrtf(var + eps) * p.gam[gi];
+      sc[c] = s;
+      sh[c] = p.bet[gi] - mu * s;
+    }
+  }
+}
+constexpr int kGnAheadG = 2, kGnAheadP = 2;   // 8 groups on 4 half-waves; 33 - 64 chunks per clip (the workload: 44 and 59)
+
 // four consecutive channels of one position (epilogue granularity)
 template <typename T> struct K4;
 template <> struct K4<bf16> {
@@ -677,9 +749,18 @@ template <typename T> hipError_t thin_dispatch(const ConvThinArgs &a, hipStream_
 // the order 16s + 8*(j >> 2) + 4*half + (j & 3), so the weight rows (A operand, staged in LDS) are read with the same
 // permutation.  The context channels follow as ordinary 8-channel slots.
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T, int C, int C2, bool X3 = false>
-__global__ __launch_bounds__(X3 ? 512 : 1024) void thin_tail_kernel(const ThinTailArgs a) {
+//
+// AHEAD (16-bit, 32 / 64 channels; tail_go chooses it for small workgroups): every global read of the workgroup before the first wait.
+// Built for at most 8 waves, which is what thin_max_waves gives these levels in the product build (tail_waves clamps the tuning hooks):
+// 256 registers per lane, room for a thread's weight vectors in flight (below).  Without it the weights and statistics come from loops.
+template <typename T, int C> constexpr bool tail_ahead() { return sizeof(T) == 2 && C >= 32; }
+// weight vectors a thread keeps in flight per round trip: what 4 waves need (C = C2 = 64: 2560 / 256; C = C2 = 32: 640 / 256)
+template <int C> constexpr int tail_wb() { return C >= 64 ? 10 : 4; }
+
+template <typename T, int C, int C2, bool X3 = false, bool AHEAD = false>
+__global__ __launch_bounds__((X3 || AHEAD) ? 512 : 1024) void thin_tail_kernel(const ThinTailArgs a) {
   static_assert(!X3 || sizeof(T) == 4, "split mode: fp32 activations");
+  static_assert(!AHEAD || tail_ahead<T, C>(), "up-front staging: the 16-bit MFMA levels");
   constexpr int E = 8;
   constexpr int QC = C / E;
   constexpr int S2 = 3 * QC, NST2 = (S2 + 1) / 2;     // conv2: slots / MFMA steps
@@ -727,6 +808,78 @@ __global__ __launch_bounds__(X3 ? 512 : 1024) void thin_tail_kernel(const ThinTa
     const bool ok = idx < total && pos >= 0 && pos < a.L;
     xin[i] = ok ? K8<T>::load(src + ((size_t)b * a.L + pos) * C + q * E) : K8<T>::zero();
   }
+  if constexpr (AHEAD) {
+    // Issue order = arrival order: rows (above), statistics / modulation operands, weights.  The statistics are folded while the
+    // weights are still on their way (as compiled the first wait lets all but the first two weight vectors stay out: the slots are
+    // conditional, so the wait counts only the certain ones), then the weights go to LDS: one round trip for all of it where a loop of
+    // load -> wait -> ds_write paid one per vector (18 per workgroup at rw = 64, C = 64).
+    // (a) modulation and bias operands of channel tid (clamped: every thread reads, threads < C store)
+    const int tc = min(tid, C - 1);
+    const float m_sc = a.ss[(size_t)b * a.ss_ld + tc], m_sh = a.ss[(size_t)b * a.ss_ld + C + tc];
+    const float m_b2 = a.bias2[tc], m_b3 = a.bias3[tc], m_ba = a.badd ? a.badd[(size_t)b * a.badd_ld + tc] : 0.f;
+    // (b) GroupNorm chunk partials of h, first round of groups
+    const float *sb = a.stats_in + (size_t)b * a.nch_in * a.G * 2;
+    const int hw = tid >> 5, nhw = blockDim.x >> 5;
+    GnAhead<kGnAheadG, kGnAheadP> gp;
+    gn_ahead_load(gp, sb, a.gamma, a.beta, a.G, a.nch_in, cpg, 0, hw, nhw, l32);
+    // (c) weights: vector i of the two packed matrices, [C][K2 / 8] then [C][K3 / 8]; thread tid takes base + j * blockDim + tid.
+    // A slot whose first index is past the end is skipped (uniform); within a slot the address is clamped and the store predicated.
+    constexpr int W2V = C * (K2 / E), WV = W2V + C * (K3 / E);
+    const T *w2g = static_cast<const T *>(a.w2), *w3g = static_cast<const T *>(a.w3);
+    auto wsrc = [&](int i) -> const T * {
+      if (i < W2V) {
+        const int r = i / (K2 / E), v = i - r * (K2 / E);
+        return w2g + (size_t)r * K2 + v * E;
+      }
+      const int i3 = i - W2V, r = i3 / (K3 / E), v = i3 - r * (K3 / E);
+      return w3g + (size_t)r * K3 + v * E;
+    };
+    auto wdst = [&](int i) -> T * {
+      if (i < W2V) {
+        const int r = i / (K2 / E), v = i - r * (K2 / E);
+        return w2s + r * P2 + v * E;
+      }
+      const int i3 = i - W2V, r = i3 / (K3 / E), v = i3 - r * (K3 / E);
+      return w3s + r * P3 + v * E;
+    };
+    constexpr int WB = tail_wb<C>();
+    K8<T> wq[WB];
+    auto w_issue = [&](int base) {
+#pragma unroll
+      for (int j = 0; j < WB; ++j) {
+        const int first = base + j * (int)blockDim.x;
+        wq[j] = first < WV ? K8<T>::load(wsrc(min(first + tid, WV - 1))) : K8<T>::zero();
+      }
+    };
+    auto w_store = [&](int base) {
+#pragma unroll
+      for (int j = 0; j < WB; ++j) {
+        const int i = base + j * (int)blockDim.x + tid;
+        if (i < WV) wq[j].store(wdst(i));
+      }
+    };
+    w_issue(0);
+    gn_ahead_fold<FAST>(gp, sb, a.G, a.nch_in, a.chunk_in, a.L, cpg, a.eps_gn, 0, hw, nhw, l32, sc, sh);
+    if (tid < C) {
+      lsc[tid] = 1.0f + m_sc;
+      lsh[tid] = m_sh;
+      ep[tid] = m_b2;
+      ep[64 + tid] = m_b3 + m_ba;
+    }
+    w_store(0);
+    // what one round does not cover: workgroups below 4 waves only if a launch asks for them (tail_waves), more than kGnAheadG groups
+    // per half-wave
+    for (int base = WB * (int)blockDim.x; base < WV; base += WB * (int)blockDim.x) {
+      w_issue(base);
+      w_store(base);
+    }
+    for (int g0 = kGnAheadG * nhw; g0 < a.G; g0 += kGnAheadG * nhw) {
+      gn_ahead_load(gp, sb, a.gamma, a.beta, a.G, a.nch_in, cpg, g0, hw, nhw, l32);
+      gn_ahead_fold<FAST>(gp, sb, a.G, a.nch_in, a.chunk_in, a.L, cpg, a.eps_gn, g0, hw, nhw, l32, sc, sh);
+    }
+  } else {
+  // fp32 / split-operand instantiations, the 8-channel MFMA fallback and the large 16-bit workgroups (tail_small) keep their loops: the
+  // fp32 vectors are twice as wide and those kernels already spill.
   // weights -> LDS (rows of the packed [C][K] matrices, 8 elements per thread and pass)
   for (int i = tid; i < C * (K2 / E); i += blockDim.x) {
     const int r = i / (K2 / E), v = i - r * (K2 / E);
@@ -755,6 +908,7 @@ __global__ __launch_bounds__(X3 ? 512 : 1024) void thin_tail_kernel(const ThinTa
     lsh[tid] = a.ss[(size_t)b * a.ss_ld + C + tid];
     ep[tid] = a.bias2[tid];
     ep[64 + tid] = a.bias3[tid] + (a.badd ? a.badd[(size_t)b * a.badd_ld + tid] : 0.f);
+  }
   }
   __syncthreads();
 #pragma unroll
@@ -1064,23 +1218,54 @@ template <typename T> size_t tail_lds_bytes(int C, int C2, int rw) {
          ((size_t)C * (3 * C + 8) + (size_t)C * (C + C2 + 8) + (size_t)(rw + 4) * (C + 8)) * sizeof(T);
 }
 
-template <typename T, int C, int C2, bool X3 = false> hipError_t tail_go(const ThinTailArgs &a, hipStream_t s) {
+// Which 16-bit launches take the up-front staging (AHEAD): the small workgroups, where the serial round trips were most of the kernel --
+// up to 4 tiles at 64 channels, up to 6 at 32 (configs[1]: rw = 64 and 192).  Larger workgroups amortise the staging over more tiles
+// and run two to a CU at batch 32, which the 157 registers of the AHEAD form at 64 channels do not always allow (6-wave workgroups
+// land 2 + 2 + 1 + 1 on the SIMDs): with every 16-bit launch on the AHEAD form configs[2] and configs[3] measured 0.5 % and 1 % below
+// the parent (profiles/thin_tail_round_trip_ab.txt), so those keep the loops.
+static bool tail_small(int C, int rw) { return (rw + 31) / 32 <= (C >= 64 ? 4 : 6); }
+
+// Waves of a tail launch: one per 32-position tile up to the level's maximum.  The instantiations built for 8 waves (split mode, AHEAD)
+// never get more, whatever the tuning hooks ask thin_max_waves for.  AHEAD launches get at least 4: the waves beyond the tiles only
+// help staging the weights (2304 - 2560 vectors at 64 channels: 9 - 10 per thread on 4 waves, one round of tail_wb), pass the barriers
+// and skip the tile loop.  Results do not depend on the count.  Measured against rounds of tail_wb on the workgroup's own 2 waves
+// (tuning hook SF_THIN_TAIL_MINWAVES=1), bf16 64 / 32 at rw = 64, HIP events around the launch inside one evaluation of configs[1]:
+// 13.9 us with the floor, 16.7 us with two rounds, 21.3 us before (profiles/thin_tail_round_trip_launches.txt).
+static int tail_waves(bool ahead, bool x3, int C, int rw) {
+  static const int floor_w = [] {
+    const char *e = tune_env("SF_THIN_TAIL_MINWAVES");
+    const int w = e ? atoi(e) : 4;
+    return w < 1 ? 1 : (w > 8 ? 8 : w);
+  }();
+  int nw = (rw + 31) / 32;
+  if (nw > thin_max_waves(C)) nw = thin_max_waves(C);
+  if ((ahead || x3) && nw > 8) nw = 8;
+  if (ahead && nw < floor_w) nw = floor_w;
+  return nw;
+}
+
+template <typename T, int C, int C2, bool X3, bool AHEAD> hipError_t tail_launch(const ThinTailArgs &a, hipStream_t s) {
   const size_t lds = tail_lds_bytes<T>(C, C2, a.rw);
-  auto kern = thin_tail_kernel<T, C, C2, X3>;
+  auto kern = thin_tail_kernel<T, C, C2, X3, AHEAD>;
   if (lds > 64 * 1024) {
-    static bool raised = false;
+    static bool raised = false;   // per instantiation
     if (!raised) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e != hipSuccess) return e;
       raised = true;
     }
   }
-  int nw = (a.rw + 31) / 32;
-  if (nw > thin_max_waves(C)) nw = thin_max_waves(C);
-  if (X3 && nw > 8) nw = 8;
+  const int nw = tail_waves(AHEAD, X3, C, a.rw);
   if ((a.rw + 2) * (C / 8) > 6 * nw * 64) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kern, dim3(a.B * a.nchw), dim3(nw * 64), lds, s, a);
   return hipGetLastError();
+}
+
+template <typename T, int C, int C2, bool X3 = false> hipError_t tail_go(const ThinTailArgs &a, hipStream_t s) {
+  if constexpr (tail_ahead<T, C>()) {
+    if (tail_small(C, a.rw)) return tail_launch<T, C, C2, X3, true>(a, s);
+  }
+  return tail_launch<T, C, C2, X3, false>(a, s);
 }
 
 template <typename T> hipError_t tail_dispatch(const ThinTailArgs &a, hipStream_t s) {
@@ -1101,8 +1286,7 @@ bool thin_tail_supported(int dt, const ThinTailArgs &a) {
   if (a.C == 8 ? cpg != 1 : (cpg != 4 && cpg != 8)) return false;
   if (!a.ss || !a.stats_in) return false;
   {
-    int nw = (a.rw + 31) / 32;
-    if (nw > thin_max_waves(a.C)) nw = thin_max_waves(a.C);
+    const int nw = tail_waves(dt != F32 && a.C >= 32 && tail_small(a.C, a.rw), dt == F32 && a.x3, a.C, a.rw);
     if ((a.rw + 2) * (a.C / 8) > 6 * nw * 64) return false;
   }
   const size_t lds = dt == F32 ? tail_lds_bytes<float>(a.C, a.C2, a.rw) : tail_lds_bytes<bf16>(a.C, a.C2, a.rw);
