@@ -668,6 +668,63 @@ int sf_vggish_forward(sf_vggish *h, const float *examples, int n, float *embeddi
 int sf_op_maxpool2x2_cl(const float *x, int64_t n, int H, int W, int ld, float *y, void *stream);
 int sf_op_moments(const float *x, int64_t n, int D, double *sum, double *scatter, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CLAP audio embedder (syncfusion_amd/clap.py)
+ *   replaces: laion_clap.CLAP_Module(enable_fusion=False, amodel='HTSAT-tiny').get_audio_embedding_from_data(x, use_tensor=True)
+ *   (exp/model/diffusion.yaml:45-48, main/module_diffusion.py:64-67): the log-mel "image", a Swin transformer and a two-layer projection.
+ *   The mel power itself comes from sf_logmel_forward.  All tensors fp32, contiguous, on the device; fp32 MFMA GEMMs, fp32 accumulation.
+ *
+ * sf_op_logmel_image   mel_power (B, n_mels, T) -> image (B, S, S), S = n_mels ratio:  v[f][t] = 10 log10(max(P, amin)) scale[f] + shift[f]
+ *     (one fma; the BatchNorm of the mel bins folded by the caller), stretched along time to S ratio frames when T is smaller (bicubic,
+ *     PyTorch's kernel: A = -0.75, align_corners, clamped borders; T == S ratio copies), folded: image[r n_mels + f][t'] = v[f][r S + t'].
+ *     A stretch over equal values (the zero-padded tail of a short clip: P <= amin) is exact: fma(fp32(10 log10 amin), scale, shift).
+ *     Refused before any HIP call: null pointers, B, n_mels, ratio < 1, T < 2, amin <= 0 (SF_ERR_INVALID); S > 4096, S ratio > 32768,
+ *     T > S ratio (nothing is shrunk), a tensor of 2^31 elements or more (SF_ERR_SHAPE).
+ * sf_op_window_attention   qkv (B H W, 3 C) rows in raster order, columns [q | k | v] each (heads, D) -> out (B H W, C): attention inside
+ *     8 x 8 windows of the map rolled by (-shift, -shift), softmax(q k^T D^-1/2 + bias_table[(dy + 7) 15 + dx + 7][head] + mask) v with
+ *     (dy, dx) = query - key inside the window; shifted windows add mask_value between tokens of different regions (region 3 hr + wr,
+ *     hr / wr in {0, 1, 2} for a rolled-frame coordinate < H - 8, < H - 4, else).  Partition, roll and their inverses are index arithmetic:
+ *     nothing is copied and no mask tensor is read.  bias_table (225, heads).  One wave per (clip, window, head), fixed-order sums: a
+ *     clip's rows do not depend on the batch.  Refused before any HIP call: null pointers, arguments < 1 (SF_ERR_INVALID); heads that do
+ *     not divide C, H or W no multiple of 8, a shift with H or W == 8, 2^31 elements or more (SF_ERR_SHAPE); a head dim that is no multiple
+ *     of 4 or above 32, a shift other than 0 or 4 (SF_ERR_UNSUPPORTED).
+ * sf_clap_audio_create   the network behind the image.  Named weights (DEVICE pointers, copied before the call returns), with every
+ *     LayerNorm affine already folded into the weights that follow it (clap.py does that in fp64):
+ *       patch.w (E, 16)  patch.b  patch.g  patch.beta                         Conv2d(1, E, 4, 4) + LayerNorm(E)
+ *       s{i}.b{j}.qkv.w (3 C, C)  .qkv.b   .rpb (225, heads)  .proj.w (C, C)  .proj.b
+ *       s{i}.b{j}.fc1.w (r C, C)  .fc1.b   .fc2.w (C, r C)    .fc2.b          C = E 2^i, r = mlp_ratio
+ *       s{i}.merge.w (2 C, 4 C)   s{i}.merge.b                                 every stage but the last
+ *       head.g  head.beta  proj0.w (J, C_last)  proj0.b  proj2.w (J, J)  proj2.b
+ *     block j of a stage is shifted by window / 2 for odd j unless the stage's map is one window.  Refused before any HIP call: null
+ *     pointers, counts out of range (SF_ERR_INVALID); a window other than 8, a head dim that is no multiple of 4 or above 32
+ *     (SF_ERR_UNSUPPORTED); spec_size no multiple of 32 2^(stages - 1), embed_dim no multiple of 32 in 32 .. 256, a final width or
+ *     joint_dim above 1024, more than 256 final tokens (SF_ERR_SHAPE); a missing or mis-sized weight (SF_ERR_MISSING_WEIGHT, named).
+ * sf_clap_audio_max_batch / sf_clap_audio_workspace_bytes   the largest B of one call and the workspace of B clips (-1 outside 1 .. max).
+ * sf_clap_audio_forward   image (B, S, S) -> embedding (B, joint_dim).  taps: NULL, or n_stages + 1 device pointers (each may be NULL)
+ *     that receive the token matrix behind the patch embed and behind every stage (after its PatchMerging), for tests.  Refused before
+ *     any HIP call: null pointers, B < 1 (SF_ERR_INVALID), B above the maximum (SF_ERR_SHAPE), a workspace below the query
+ *     (SF_ERR_WORKSPACE), a GEMM shape no kernel takes (SF_ERR_UNSUPPORTED).  Nothing is allocated and nothing synchronises.
+ * sf_clap_audio_describe   HOST-only: one line per GEMM of the network at batch B with the kernel family the dispatcher gives it. */
+#define SF_CLAP_MAX_STAGES 8
+typedef struct {
+  int32_t spec_size, embed_dim, n_stages;
+  int32_t depths[SF_CLAP_MAX_STAGES], heads[SF_CLAP_MAX_STAGES];
+  int32_t window, mlp_ratio, joint_dim;
+  float ln_eps, mask_value;
+  int32_t projection_relu, normalize;
+} sf_clap_audio_config;
+typedef struct sf_clap_audio sf_clap_audio;
+int sf_op_logmel_image(const float *mel_power, int B, int n_mels, int T, int ratio, const float *scale, const float *shift, float amin, float *image,
+                       void *stream);
+int sf_op_window_attention(const float *qkv, int B, int H, int W, int C, int heads, int shift, const float *bias_table, float mask_value, float *out,
+                           void *stream);
+int sf_clap_audio_create(const sf_clap_audio_config *cfg, const sf_tensor *weights, int n_weights, void *stream, sf_clap_audio **out);
+void sf_clap_audio_destroy(sf_clap_audio *h);
+int sf_clap_audio_max_batch(const sf_clap_audio *h);
+int64_t sf_clap_audio_workspace_bytes(const sf_clap_audio *h, int B);
+int sf_clap_audio_forward(sf_clap_audio *h, const float *image, int B, float *embedding, float *const *taps, void *ws, int64_t ws_bytes, void *stream);
+int sf_clap_audio_describe(const sf_clap_audio_config *cfg, int B, char *text /*host*/, int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

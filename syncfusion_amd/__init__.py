@@ -6,12 +6,13 @@ Public surface = the reference's own: ``DiffusionModel`` 
 runs in ``lib/libsyncfusion_amd.so`` (hand-written HIP, C ABI in include/syncfusion_amd.h).
 """
 from . import _lib  # noqa: F401
-from . import audio_features, autograd, evaluation, fad, frame_transforms, onset_test, onset_training, shards, training, video_chunks  # noqa: F401
+from . import audio_features, autograd, clap, evaluation, fad, frame_transforms, onset_test, onset_training, shards, training, video_chunks  # noqa: F401
 from .config import instantiate, instantiate_class, instantiate_frames_transforms, instantiate_model_yaml
 from .diffusion import DiffusionModel, LinearSchedule, UNetV0, VDiffusion, VSampler
 from .audio_features import MelSpectrogram, mel_filterbank, onset_detect, onset_strength
 from .encoder1d import Encoder1d
 from .evaluation import evaluate_onsets
+from .clap import ClapAudioConfig, ClapAudioEmbedder
 from .fad import VGGish, VGGishConfig, embedding_statistics, evaluate_fad, frechet_distance
 from .generation import generate_batch, generate_dataset, prepare_gt_for_fad
 from .module import Model, RandomEmbedder
@@ -28,5 +29,6 @@ __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule
            "allreduce_gradients", "frame_transforms", "instantiate_class", "instantiate_frames_transforms",
            "audio_features", "evaluation", "MelSpectrogram", "mel_filterbank", "onset_detect", "onset_strength", "evaluate_onsets",
            "fad", "VGGish", "VGGishConfig", "embedding_statistics", "frechet_distance", "evaluate_fad",
-           "onset_test", "OnsetTestStage", "annotation_rows", "pack_onset_preds", "test_onset_model", "prepare_gt_for_fad"]
+           "onset_test", "OnsetTestStage", "annotation_rows", "pack_onset_preds", "test_onset_model", "prepare_gt_for_fad",
+           "clap", "ClapAudioConfig", "ClapAudioEmbedder"]
 __version__ = "0.1.0"

@@ -53,6 +53,17 @@ class VConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "T", "Hi", "Wi", "cin", "cin_ld", "cout", "cout_ld", "kt", "kh", "kw", "sh", "sw", "pt", "ph", "pw")]
 
 
+SF_CLAP_MAX_STAGES = 8
+
+
+class ClapAudioEngineConfig(C.Structure):
+    """sf_clap_audio_config: the Swin network behind the log-mel image (syncfusion_amd/clap.py)."""
+    _fields_ = [("spec_size", C.c_int32), ("embed_dim", C.c_int32), ("n_stages", C.c_int32),
+                ("depths", C.c_int32 * SF_CLAP_MAX_STAGES), ("heads", C.c_int32 * SF_CLAP_MAX_STAGES),
+                ("window", C.c_int32), ("mlp_ratio", C.c_int32), ("joint_dim", C.c_int32),
+                ("ln_eps", C.c_float), ("mask_value", C.c_float), ("projection_relu", C.c_int32), ("normalize", C.c_int32)]
+
+
 # every symbol include/syncfusion_amd.h declares: (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -214,6 +225,20 @@ SYMBOLS = {
     "sf_vggish_forward": (_I, [_P, _P, _I, _P, _P, _P, _L, _P]),
     "sf_op_maxpool2x2_cl": (_I, [_P, _L, _I, _I, _I, _P, _P]),
     "sf_op_moments": (_I, [_P, _L, _I, _P, _P, _P]),
+    # the CLAP audio embedder (syncfusion_amd/clap.py)
+    # (mel_power, B, n_mels, T, ratio, scale, shift, amin, image, stream)
+    "sf_op_logmel_image": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P]),
+    # (qkv, B, H, W, C, heads, shift, bias_table, mask_value, out, stream)
+    "sf_op_window_attention": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _F, _P, _P]),
+    # (cfg, weights, n_weights, stream, out)
+    "sf_clap_audio_create": (_I, [C.POINTER(ClapAudioEngineConfig), C.POINTER(SfTensor), _I, _P, C.POINTER(_P)]),
+    "sf_clap_audio_destroy": (None, [_P]),
+    "sf_clap_audio_max_batch": (_I, [_P]),
+    "sf_clap_audio_workspace_bytes": (_L, [_P, _I]),
+    # (h, image, B, embedding, taps, ws, ws_bytes, stream)
+    "sf_clap_audio_forward": (_I, [_P, _P, _I, _P, _P, _P, _L, _P]),
+    # (cfg, B, text_host, capacity)
+    "sf_clap_audio_describe": (_I, [C.POINTER(ClapAudioEngineConfig), _I, C.c_char_p, _L]),
 }
 
 _lib: Optional[C.CDLL] = None
