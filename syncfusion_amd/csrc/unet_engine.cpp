@@ -898,8 +898,7 @@ struct Exec {
   }
 
   // rows x K GEMM on per-clip vectors (time MLP, modulation, cross-attention collapse)
-  void dense(const ConvW &w, const void *src, int src_ld, int rows, void *out, int out_ld, int act, bool out_f32, int col0 = 0,
-             int ncols = -1) {
+  void dense(const ConvW &w, const void *src, int src_ld, int rows, void *out, int out_ld, int act, bool out_f32) {
     ConvGemmArgs a;
     a.src = src;
     a.src_ld = src_ld;
@@ -909,8 +908,6 @@ struct Exec {
     a.out_ld = out_ld;
     a.act = act;
     a.out_f32 = out_f32 ? 1 : 0;
-    (void)col0;
-    (void)ncols;
     conv(w, a, u.dt, out_f32 ? F32 : u.dt);
   }
 
@@ -921,352 +918,480 @@ struct Exec {
           [&] { SF_HIP(launch_gn_stats(u.dt, x, C, p.Bt, l.L, C, u.cfg.resnet_groups, gp.nch, gp.chunk_rows, p.slab, s)); });
   }
 
-  // One item-group: Resnet -> Modulation -> InjectChannels -> [Attention] -> [CrossAttention]
-  // cur is consumed; returns the buffer that holds the result.  tA / tB are the two free buffers.
-  // next: the item group that consumes this one's output at the same level (nullptr: a down / up convolution follows)
-  void group(const Group &g, int d, void *&cur, void *&tA, void *&tB, const std::string &tapname, const Group *next = nullptr) {
+  // ---------------------------------------------------------------------------------------------------
+  // The item path.  One item group: ResnetItem -> Modulation -> InjectChannels -> [Attention] -> [CrossAttention]
+  //   h = Conv3(SiLU(GN(x)));  y = x + Conv3(SiLU(GN(h)));  m = LN_C(y; 1e-6) * (1 + scale) + shift;  z = m + Conv1x1(cat[m, ctx]) (+ bias)
+  // item_plan decides how the item runs before anything is launched, one function per chain issues the launches up to z, and group()
+  // adds the self-attention and rotates the level's buffers.  The GEMM arguments come from one builder per launch (*_args): item_plan
+  // asks its questions about what the chains will launch.
+  // ---------------------------------------------------------------------------------------------------
+  enum Chain {
+    THIN,        // conv_thin x 3: conv1 [GN+SiLU in, statistics of h out], conv2 [GN+SiLU in, + x], inject [LN-modulate in, + itself, statistics out]
+    THIN_TAIL,   // conv_thin conv1, then conv2 + Modulation + InjectChannels in one thin_tail launch
+    WIDE,        // gn_silu, GEMM, gn_silu, GEMM (fuse_act: gn_stats and the activation in the A-load), then ln_modulate + InjectChannels or the LN-folded InjectChannels
+    CB,          // channel-block split-K chain (conv_cb.hip): [gn_silu,] conv_cb, cb_reduce_gn, conv_cb, cb_reduce_ln, InjectChannels
+    CBD          // direct channel-block chain at C = 128: gn_silu, conv_cb_gn, conv_cb_ln, InjectChannels
+  };
+  struct ItemPlan {
+    Chain chain = WIDE;
+    bool fuse_act = false;    // WIDE, C <= 64 (at most two column tiles): GroupNorm+SiLU stays in the convolutions' A-load instead of a gn_silu copy
+    bool fuse_mod = false;    // WIDE: conv2 leaves row partials and InjectChannels applies Modulation's LayerNorm to its operand (no ln_modulate launch)
+    bool fuse_attn = false;   // InjectChannels leaves row partials and the qkv projection folds the attention pre-norm (no ln_modulate launch)
+    int short_k = 0;          // ConvGemmArgs::short_k of InjectChannels (CBD: K = 160 on the 32x32 kernel the LN-folded form ran on, not the 64x64 tile)
+    bool thin() const { return chain == THIN || chain == THIN_TAIL; }
+  };
+  struct Item {   // one item at work
+    const Group &g;
+    const Group *next;   // the item that consumes this one's output at the same level (nullptr: a down / up convolution follows)
+    int d;
+    const Level &l;
+    const Block &b;
+    int C, G;
+    void *x, *f0, *f1;   // the input and the level's two free buffers.  Every chain leaves z in f1; f0 and l.act are scratch, x stays intact
+  };
+  Item item_of(const Group &g, int d, void *x, void *f0, void *f1, const Group *next) const {
+    return Item{g, next, d, p.lv[d], u.blocks[d], p.lv[d].C, u.cfg.resnet_groups, x, f0, f1};
+  }
+  // per-row LayerNorm partials of the wide levels: of y (conv2 -> InjectChannels) and of z (InjectChannels -> qkv)
+  float *rp_y() const { return p.rowpart; }
+  float *rp_z() const { return p.rowpart + p.rowpart_half; }
+
+  ConvGemmArgs level_args(const Level &l, const void *src, int src_ld, void *out, int out_ld) const {
+    ConvGemmArgs a;
+    a.src = src;
+    a.src_ld = src_ld;
+    a.M = (int)l.rows;
+    a.Lout = a.Lsrc = l.L;
+    a.out = out;
+    a.out_ld = out_ld;
+    return a;
+  }
+  // conv1 / conv2 of the wide chain on `in`: its activated copy l.act, or (fuse_act) the raw rows with GroupNorm+SiLU from gn_stats' slab
+  ConvGemmArgs conv3_args(const Item &it, bool fuse_act, const void *in, void *out, const float *gam, const float *bet, const void *res) const {
+    ConvGemmArgs a = level_args(it.l, fuse_act ? in : it.l.act, it.C, out, it.C);
+    a.pad = 1;
+    a.res = res;
+    a.res_ld = it.C;
+    if (fuse_act) {
+      const GnPlan gp = gn_plan(p.Bt, it.l.L, it.C);
+      a.pro = 1;
+      a.G = it.G;
+      a.nch = gp.nch;
+      a.chunk_rows = gp.chunk_rows;
+      a.stats = p.slab;
+      a.gamma = gam;
+      a.beta = bet;
+      a.eps = 1e-5f;
+    }
+    return a;
+  }
+  // InjectChannels -> it.f1: z = m + Conv1x1(cat[m, ctx]) (+ collapsed cross-attention bias when no self-attention follows).
+  // ln: src holds y and the GEMM makes m of operand and residual on the fly from y's row partials (Modulation + InjectChannels in one GEMM)
+  ConvGemmArgs inject_args(const Item &it, const void *src, bool ln, int short_k) const {
+    ConvGemmArgs a = level_args(it.l, src, it.C, it.f1, it.C);
+    a.src2 = it.l.ctx;
+    a.src2_ld = it.b.ctx_ld;
+    a.res = src;
+    a.res_ld = it.C;
+    a.short_k = short_k;
+    if (it.g.cross && !it.g.attn) {
+      a.badd = p.ca_all + it.g.ca_off;
+      a.badd_ld = u.ca_ld;
+    }
+    if (ln) {
+      a.ln_part = rp_y();
+      a.ln_nt = it.C / 32;
+      a.ln_ss = p.mod_all + it.g.mod_off;
+      a.ln_ss_ld = p.mod_stride;
+      a.ln_eps = 1e-6f;
+      a.res_ln = 1;
+    }
+    return a;
+  }
+  // packed q | k | v projection of the pre-normed rows.  ln: src holds raw z; it goes through the MFMAs as it is and the epilogue applies
+  // rstd * (acc - mean * colsum) from z's row partials (the two pre-norms share (mean, rstd); their affines are folded into the weights)
+  ConvGemmArgs qkv_args(const Item &it, const void *src, bool ln) const {
+    ConvGemmArgs a = level_args(it.l, src, it.C, it.l.qkv, 3 * u.hd);
+    if (ln) {
+      a.ln_part = rp_z();
+      a.ln_nt = it.C / 32;
+      a.ln_eps = 1e-5f;
+      a.ln_colsum = it.g.qkv_colsum;
+    }
+    return a;
+  }
+  // attention output projection: out = z + W_o ao (+ collapsed cross-attention bias)
+  ConvGemmArgs attn_out_args(const Group &g, int d, void *out, const void *z) const {
+    ConvGemmArgs a = level_args(p.lv[d], p.lv[d].ao, u.hd, out, p.lv[d].C);
+    a.res = z;
+    a.res_ld = p.lv[d].C;
+    if (g.cross) {
+      a.badd = p.ca_all + g.ca_off;
+      a.badd_ld = u.ca_ld;
+    }
+    return a;
+  }
+  // the thin chains' launches: conv1 x -> h, conv2 h -> y, inject y -> f1, or conv1 and `tail` (h -> f1)
+  struct ThinArgs {
+    ConvThinArgs conv1, conv2, inject;
+    ThinTailArgs tail;
+  };
+  static const void *thin_w(const ConvW &w) { return w.direct ? w.wt : w.w; }
+  ThinArgs thin_args(const Item &it, bool tail) const {
+    const Group &g = it.g;
+    const ThinPlan tp = conv_thin_plan(p.Bt, it.l.L, it.C);
+    float *sA = p.slab, *sB = p.slab + p.slab_half;   // statistics of the item's input / output, and of h
+    void *h = tail ? it.f0 : it.f1, *y = it.f0;
+    ThinArgs r;
+    ConvThinArgs base;
+    base.B = p.Bt;
+    base.L = base.Ls = it.l.L;
+    base.C = base.N = it.C;
+    base.G = it.G;
+    base.rw = tp.rw;
+    base.nchw = tp.nchw;
+    base.nch_in = tp.nchw;
+    base.chunk_in = tp.rw;
+    base.src_ld = base.out_ld = base.res_ld = it.C;
+    base.x3 = u.x3 ? 1 : 0;
+    base.taps = 3;
+    base.pro = 1;
+    r.conv1 = r.conv2 = base;
+    r.conv1.src = it.x;
+    r.conv1.w = thin_w(g.conv1);
+    if (g.conv1.direct) r.conv1.w32 = static_cast<const float *>(g.conv1.w);
+    r.conv1.bias = g.conv1.bias;
+    r.conv1.gamma = g.gn1_g;
+    r.conv1.beta = g.gn1_b;
+    r.conv1.stats_in = sA;
+    r.conv1.stats_out = sB;
+    r.conv1.out = h;
+    r.conv2.src = h;
+    r.conv2.w = thin_w(g.conv2);
+    if (g.conv2.direct) r.conv2.w32 = static_cast<const float *>(g.conv2.w);
+    r.conv2.bias = g.conv2.bias;
+    r.conv2.gamma = g.gn2_g;
+    r.conv2.beta = g.gn2_b;
+    r.conv2.stats_in = sB;
+    r.conv2.res = it.x;
+    r.conv2.out = y;
+    ConvThinArgs &a = r.inject = base;
+    a.taps = 1;
+    a.pro = 2;
+    a.C2 = g.inject.direct ? pad_to(g.inject.cin2, 8) : g.inject.cin2;
+    a.src = y;
+    a.src2 = it.l.ctx;
+    a.src2_ld = it.b.ctx_ld;
+    a.w = thin_w(g.inject);
+    a.bias = g.inject.bias;
+    a.ss = p.mod_all + g.mod_off;
+    a.ss_ld = p.mod_stride;
+    a.eps = 1e-6f;
+    a.res_self = 1;
+    if (g.cross && !g.attn) {
+      a.badd = p.ca_all + g.ca_off;
+      a.badd_ld = u.ca_ld;
+    }
+    a.stats_out = g.attn ? nullptr : sA;
+    a.out = it.f1;
+    ThinTailArgs &t = r.tail;   // conv2 and inject above as one launch
+    t.x3 = base.x3;
+    t.h = h;
+    t.x = it.x;
+    t.ctx = a.src2;
+    t.ctx_ld = a.src2_ld;
+    t.w2 = r.conv2.w;
+    t.w3 = a.w;
+    if (g.conv2.direct && g.inject.direct) {
+      t.w2_32 = static_cast<const float *>(g.conv2.w);
+      t.w3_32 = static_cast<const float *>(g.inject.w);
+      t.c2real = g.inject.cin2;
+    }
+    t.bias2 = g.conv2.bias;
+    t.bias3 = g.inject.bias;
+    t.gamma = g.gn2_g;
+    t.beta = g.gn2_b;
+    t.stats_in = sB;
+    t.ss = a.ss;
+    t.ss_ld = a.ss_ld;
+    t.badd = a.badd;
+    t.badd_ld = a.badd_ld;
+    t.out = it.f1;
+    t.stats_out = a.stats_out;
+    t.B = p.Bt;
+    t.L = it.l.L;
+    t.C = it.C;
+    t.C2 = a.C2;
+    t.G = it.G;
+    t.nch_in = t.nchw = tp.nchw;
+    t.chunk_in = t.rw = tp.rw;
+    return r;
+  }
+
+  // The only place of the item path that asks what the kernels cover.  A pure function of the engine, the Plan and the group: which buffers
+  // the item will rotate through does not enter (the builders are given the level's own three).
+  ItemPlan item_plan(const Group &g, int d) const {
     const Level &l = p.lv[d];
-    const Block &b = u.blocks[d];
-    const int C = l.C, G = u.cfg.resnet_groups;
-    // ResnetItem: x + Conv3(SiLU(GN(Conv3(SiLU(GN(x)))))).  GroupNorm+SiLU is materialised once per conv
-    // (gn_silu) rather than applied in the GEMM's A-load: the activation would otherwise be recomputed for every
-    // column tile and tap of the wide layers.
-    // Thin levels (C <= 64: at most two column tiles) keep the activation in the conv's A-load instead
-    // (statistics from gn_stats): their tensors are long and the extra activated copy would cost more.
-    if (group_thin(g, d, cur, tA, tB)) {
-      if (!g.attn) {
-        u.dbg.tap(tapname, u.dt, cur, C, l.rows, C, s);
-        return;
+    const Item it = item_of(g, d, l.buf[0], l.buf[1], l.buf[2], nullptr);
+    const int C = l.C;
+    ItemPlan pl;
+    // Thin levels (C <= 64 on long sequences): the extra activated copy of the wide chain would cost more than the activation in the A-load
+    if (g.conv1.cin == C && g.inject.cin == C && thin_w(g.conv1) && thin_w(g.conv2) && thin_w(g.inject)) {
+      const ThinArgs t = thin_args(it, true);
+      if (t.inject.C2 <= it.b.ctx_ld && conv_thin_supported(u.dt, t.conv1) && conv_thin_supported(u.dt, t.inject)) {
+        const bool tail = !u.no_thin_tail && g.conv2.bias && g.inject.bias && thin_tail_supported(u.dt, t.tail);
+        pl.chain = tail ? THIN_TAIL : THIN;   // (self-attention behind a thin item takes the plain pre-norm launch)
+        return pl;
       }
-    } else {
-    const bool fuse_act = C <= 64;
-    GnPlan gp = gn_plan(p.Bt, l.L, C);
-    auto conv3 = [&](const ConvW &w, const void *in, void *out, const float *gam, const float *bet, const void *res, float *rowpart,
-                     const ConvW *next = nullptr) {
-      ConvGemmArgs a;
-      if (next) a.pf = pf_for(*next, (int)((l.rows + 31) / 32) * ((C + 31) / 32), l.rows);
-      if (rowpart) {
-        a.rowpart_out = rowpart;
-        a.rowpart_nt = C / 32;
-      }
-      if (fuse_act) {
-        gn(in, d, C);
-        a.src = in;
-        a.pro = 1;
-        a.G = G;
-        a.nch = gp.nch;
-        a.chunk_rows = gp.chunk_rows;
-        a.stats = p.slab;
-        a.gamma = gam;
-        a.beta = bet;
-        a.eps = 1e-5f;
-      } else {
-        a.src = l.act;
-      }
-      a.src_ld = C;
-      a.M = (int)l.rows;
-      a.Lout = a.Lsrc = l.L;
-      a.stride = 1;
-      a.pad = 1;
-      a.out = out;
-      a.out_ld = C;
-      a.res = res;
-      a.res_ld = C;
-      if (!fuse_act) {
-        // fp32x: when the convolution runs on the macro tiles, GroupNorm+SiLU writes its rows already split into fp16 (hi, lo') -- the
-        // activated tensor has no other reader -- and the GEMM spends no vector instruction on its activation operand
-        const bool xf = u.x3 && (C % 32) == 0 && conv_gemm_src_x3_ok(filled(w, a));
-        // (the chunked two-launch form of launch_gn_silu_ws was measured on the 2^18-sample shape: 97.4 vs 98.4 steps/s -- the second
-        // launch costs what the better CU fill saves -- so the engine keeps the single launch)
-        timed("gn_silu", 12.0 * l.rows * C, 3.0 * l.rows * C * dsize(u.dt),
-              [&] { SF_HIP(launch_gn_silu(u.dt, in, C, p.Bt, l.L, C, G, gam, bet, 1e-5f, l.act, C, s, pf_for(w, p.Bt * G), xf)); });
-        a.src_x3 = xf ? 1 : 0;
-      }
-      conv(w, a, u.dt, u.dt);
-    };
-    // Wide levels: the two LayerNorms of an item (Modulation before InjectChannels, the attention pre-norm) are not
-    // launched: the producing GEMM's epilogue leaves per-row (mean, M2) partials per 32-column tile, the consuming GEMM
-    // pools them and normalises (and modulates) its A operand while staging it.  Falls back to ln_modulate launches
-    // whenever a shape is outside what conv_gemm_fast / conv_gemm_wp cover.
-    float *rp_y = p.rowpart, *rp_z = p.rowpart + p.rowpart_half;
-    auto inject_args = [&](const void *src, void *out) {
-      ConvGemmArgs a;
-      a.src = src;
-      a.src_ld = C;
-      a.src2 = l.ctx;
-      a.src2_ld = b.ctx_ld;
-      a.M = (int)l.rows;
-      a.Lout = a.Lsrc = l.L;
-      a.out = out;
-      a.out_ld = C;
-      a.res = src;
-      a.res_ld = C;
-      if (g.cross && !g.attn) {
-        a.badd = p.ca_all + g.ca_off;
-        a.badd_ld = u.ca_ld;
-      }
-      return a;
-    };
-    auto qkv_args = [&](const void *src) {
-      ConvGemmArgs a;
-      a.src = src;
-      a.src_ld = C;
-      a.M = (int)l.rows;
-      a.Lout = a.Lsrc = l.L;
-      a.out = l.qkv;
-      a.out_ld = 3 * u.hd;
-      return a;
-    };
-    bool fuse_mod = false;
+    }
+    pl.fuse_act = C <= 64;
+    const bool cb_w = !pl.fuse_act && g.conv1.wcb && g.conv2.wcb && g.conv1.bias && g.conv2.bias;
+    if (l.cb && cb_w && p.cbslab) pl.chain = CB;
+    else if (l.cbd && cb_w && g.conv1.cin == C && (g.mod_off % 4) == 0 && (p.mod_stride % 4) == 0) pl.chain = CBD;   // (16-byte loads of the Modulation pair)
+    pl.short_k = pl.chain == CBD ? 1 : 0;
+    // Wide levels: the two LayerNorms of an item (Modulation before InjectChannels, the attention pre-norm) are not launched when the
+    // producing GEMM's epilogue can leave per-row (mean, M2) partials per 32-column tile and the consuming GEMM can pool them and normalise
+    // (and modulate) its A operand while staging it; ln_modulate launches whenever a shape is outside what conv_gemm_fast / conv_gemm_wp cover.
     // (measured: normalising the operand while staging costs more than the separate launch once the row is 1024 wide)
     static const int ln_fuse_maxc = [] {   // tuning hook: widest level whose Modulation LayerNorm is folded into the InjectChannels GEMM
       const char *e = tune_env("SF_LN_FUSE_MAXC");
       return e ? atoi(e) : 512;
     }();
-    if (!fuse_act && C % 32 == 0 && C <= ln_fuse_maxc && !u.no_ln_fusion) {
-      ConvGemmArgs pc;   // conv2 as it will be launched
-      pc.src = l.act;
-      pc.src_ld = C;
-      pc.M = (int)l.rows;
-      pc.Lout = pc.Lsrc = l.L;
-      pc.pad = 1;
-      pc.out = tB;
-      pc.out_ld = C;
-      pc.res = cur;
-      pc.res_ld = C;
-      ConvGemmArgs pi = inject_args(tB, tA);
-      pi.ln_part = rp_y;
-      pi.ln_nt = C / 32;
-      pi.ln_ss = p.mod_all + g.mod_off;
-      pi.ln_ss_ld = p.mod_stride;
-      pi.ln_eps = 1e-6f;
-      pi.res_ln = 1;
-      fuse_mod = conv_gemm_emits_rowpart(u.dt, filled(g.conv2, pc)) && conv_gemm_ln_ok(u.dt, filled(g.inject, pi));
-    }
-    const bool use_cb = l.cb && !fuse_act && g.conv1.wcb && g.conv2.wcb && g.conv1.bias && g.conv2.bias && p.cbslab;
-    const bool use_cbd = l.cbd && !use_cb && !fuse_act && g.conv1.wcb && g.conv2.wcb && g.conv1.bias && g.conv2.bias && g.conv1.cin == C &&
-                         (g.mod_off % 4) == 0 && (p.mod_stride % 4) == 0;   // (16-byte loads of the Modulation pair)
-    bool fuse_attn = false;
+    if (pl.chain == WIDE && !pl.fuse_act && C % 32 == 0 && C <= ln_fuse_maxc && !u.no_ln_fusion)
+      pl.fuse_mod = conv_gemm_emits_rowpart(u.dt, filled(g.conv2, conv3_args(it, false, it.f1, it.f0, g.gn2_g, g.gn2_b, it.x))) &&
+                    conv_gemm_ln_ok(u.dt, filled(g.inject, inject_args(it, it.f0, true, 0)));
     if (g.attn && C % 32 == 0 && !u.no_ln_fusion) {
-      ConvGemmArgs pq = qkv_args(tB);
-      pq.ln_part = rp_z;
-      pq.ln_nt = C / 32;
-      pq.ln_eps = 1e-5f;
-      pq.ln_colsum = g.qkv_colsum;
-      ConvGemmArgs pi = inject_args(tA, tB);
-      pi.short_k = use_cbd ? 1 : 0;
-      // the LN-folded InjectChannels kernel always writes row partials; the channel-block chain launches the PLAIN InjectChannels GEMM
-      // whatever fuse_mod says, so ask about the launch that will actually run
-      const bool inj_emits = (fuse_mod && !use_cb && !use_cbd) ? true : conv_gemm_emits_rowpart(u.dt, filled(g.inject, pi));
-      fuse_attn = inj_emits && conv_gemm_ln_ok(u.dt, filled(g.qkv, pq));
+      // (the LN-folded InjectChannels kernel always writes row partials; the channel-block chains launch the plain GEMM)
+      const bool inj_emits = pl.fuse_mod || conv_gemm_emits_rowpart(u.dt, filled(g.inject, inject_args(it, it.f0, false, pl.short_k)));
+      pl.fuse_attn = inj_emits && conv_gemm_ln_ok(u.dt, filled(g.qkv, qkv_args(it, it.f1, true)));
     }
-    if (use_cb) {
-      // Channel-block split-K chain (conv_cb.hip): the two launches that followed the convolutions anyway (GroupNorm+SiLU, LayerNorm +
-      // Modulation) sum the fp32 partial slabs; the second convolution applies GroupNorm+SiLU while staging its activation panel.
-      const int bt = p.Bt, kb = l.cb_kb, S = C / 128 / kb;
-      const double es = dsize(u.dt), rc = (double)l.rows * C;
-      const double cflops = 2.0 * rc * 3 * C, cbytes = 2.0 * rc * es + 3.0 * C * C * es;
-      const int mt = kb == 2 ? std::min(2, conv_cb_mt((int)l.rows, C, C / 2)) : conv_cb_mt((int)l.rows, C, C);
-      const int cwgs = (int)((l.rows + 32 * mt - 1) / (32 * mt)) * (C / 128) * S;
-      const CbGnPlan cgp = cb_gn_plan(l.L);
-      const int cbdt = u.x3 ? (int)F32X : u.dt;
-      ConvCbArgs a;
-      a.src_ld = C;
-      a.wp = g.conv1.wcb;
-      a.slab = p.cbslab;
-      a.B = bt;
-      a.L = l.L;
-      a.C = a.N = C;
-      a.kb = kb;
-      a.G = G;
-      a.eps = 1e-5f;
-      a.pf = pf_cb(g.conv2, cwgs);
-      if (gnpart_of == cur && wants_gnpart(d)) {
-        // the GEMM that produced `cur` left its GroupNorm tile statistics: GroupNorm+SiLU rides in conv1's panel prologue, no gn_silu launch
-        a.src = cur;
-        a.pro = 2;
-        a.stats = p.gnpart;
-        a.gamma = g.gn1_g;
-        a.beta = g.gn1_b;
-        timed("conv_cb", cflops + 12.0 * rc, cbytes, [&] { SF_HIP(launch_conv_cb(cbdt, a, s)); });
-      } else {
-        timed("gn_silu", 12.0 * rc, 3.0 * rc * es,
-              [&] { SF_HIP(launch_gn_silu(u.dt, cur, C, bt, l.L, C, G, g.gn1_g, g.gn1_b, 1e-5f, l.act, C, s, pf_cb(g.conv1, bt * G))); });
-        a.src = l.act;
-        timed("conv_cb", cflops, cbytes, [&] { SF_HIP(launch_conv_cb(cbdt, a, s)); });
-      }
-      gnpart_of = nullptr;
-      timed("cb_reduce_gn", 4.0 * rc, 2.0 * rc * es, [&] {
-        SF_HIP(launch_cb_reduce_gn(u.dt, p.cbslab, S, bt, l.L, C, g.conv1.bias, tA, C, G, p.slab, cgp, s, pf_cb(g.conv2, bt * cgp.nch * (C / 128))));
-      });
-      a.src = tA;
-      a.wp = g.conv2.wcb;
-      a.pro = 1;
-      a.nch = cgp.nch;
-      a.chunk_rows = cgp.chunk_rows;
-      a.stats = p.slab;
-      a.gamma = g.gn2_g;
-      a.beta = g.gn2_b;
-      a.pf = pf_for(g.inject, cwgs, l.rows);
+    return pl;
+  }
+
+  void thin_chain(const Item &it, bool tail) {
+    const Group &g = it.g;
+    const Level &l = it.l;
+    const int C = it.C;
+    const ThinArgs t = thin_args(it, tail);
+    const double es = dsize(u.dt), rc = (double)l.rows * C, kin = g.inject.kreal > 0 ? g.inject.kreal : g.inject.K;
+    if (stats_of != it.x)
+      timed("gn_stats", 3.0 * rc, rc * es, [&] { SF_HIP(launch_gn_stats(u.dt, it.x, C, p.Bt, l.L, C, it.G, t.conv1.nchw, t.conv1.rw, p.slab, s)); });
+    timed("conv_thin", 2.0 * rc * 3 * C, 2.0 * rc * es + 3.0 * C * C * es, [&] { SF_HIP(launch_conv_thin(u.dt, t.conv1, s)); });
+    if (tail) {
+      timed("conv_thin", 2.0 * rc * 3 * C + 2.0 * rc * kin + 8.0 * rc, 3.0 * rc * es + (double)l.rows * (kin - C) * es + (3.0 * C + kin) * C * es,
+            [&] { SF_HIP(launch_thin_tail(u.dt, t.tail, s)); });
+    } else {
+      timed("conv_thin", 2.0 * rc * 3 * C, 3.0 * rc * es + 3.0 * C * C * es, [&] { SF_HIP(launch_conv_thin(u.dt, t.conv2, s)); });
+      timed("conv_thin", 2.0 * rc * kin + 8.0 * rc, 2.0 * rc * es + (double)l.rows * (kin - C) * es + kin * C * es,
+            [&] { SF_HIP(launch_conv_thin(u.dt, t.inject, s)); });
+    }
+    stats_of = g.attn ? nullptr : it.f1;   // the last launch left the statistics of z for the next item's conv1
+  }
+
+  // GroupNorm+SiLU is materialised once per convolution (gn_silu) rather than applied in the GEMM's A-load: the activation would otherwise
+  // be recomputed for every column tile and tap of the wide layers.  fuse_act keeps it in the A-load (statistics from gn_stats).
+  // host_for: the GEMM whose weights this convolution's launch prefetches
+  void conv3(const Item &it, const ItemPlan &pl, const ConvW &w, const void *in, void *out, const float *gam, const float *bet, const void *res,
+             float *rowpart, const ConvW *host_for) {
+    const Level &l = it.l;
+    const int C = it.C;
+    ConvGemmArgs a = conv3_args(it, pl.fuse_act, in, out, gam, bet, res);
+    if (host_for) a.pf = pf_for(*host_for, (int)((l.rows + 31) / 32) * ((C + 31) / 32), l.rows);
+    if (rowpart) {
+      a.rowpart_out = rowpart;
+      a.rowpart_nt = C / 32;
+    }
+    if (pl.fuse_act) {
+      gn(in, it.d, C);
+    } else {
+      // fp32x: when the convolution runs on the macro tiles, GroupNorm+SiLU writes its rows already split into fp16 (hi, lo') -- the
+      // activated tensor has no other reader -- and the GEMM spends no vector instruction on its activation operand
+      const bool xf = u.x3 && (C % 32) == 0 && conv_gemm_src_x3_ok(filled(w, a));
+      // (the chunked two-launch form of launch_gn_silu_ws was measured on the 2^18-sample shape: 97.4 vs 98.4 steps/s -- the second
+      // launch costs what the better CU fill saves -- so the engine keeps the single launch)
+      timed("gn_silu", 12.0 * l.rows * C, 3.0 * l.rows * C * dsize(u.dt),
+            [&] { SF_HIP(launch_gn_silu(u.dt, in, C, p.Bt, l.L, C, it.G, gam, bet, 1e-5f, l.act, C, s, pf_for(w, p.Bt * it.G), xf)); });
+      a.src_x3 = xf ? 1 : 0;
+    }
+    conv(w, a, u.dt, u.dt);
+  }
+
+  // InjectChannels on m (fuse_mod: on y), the last launch of the wide and channel-block chains.  Beside z it leaves what z's consumer
+  // reads with it -- row partials (fuse_attn), GroupNorm tile statistics (channel-block levels) -- and hosts the qkv weights' prefetch
+  void inject(const Item &it, const ItemPlan &pl, const void *m) {
+    const Group &g = it.g;
+    ConvGemmArgs a = inject_args(it, m, pl.fuse_mod, pl.short_k);
+    if (pl.fuse_attn) {
+      a.rowpart_out = rp_z();
+      a.rowpart_nt = it.C / 32;
+    }
+    if (g.attn) a.pf = pf_for(g.qkv, (int)((it.l.rows + 31) / 32) * (it.C / 32), it.l.rows);
+    else if (pl.chain == CB && it.next && arm_gnpart(g.inject, a, it.d)) gnpart_of = it.f1;
+    conv(g.inject, a, u.dt, u.dt, /*ln=*/pl.fuse_mod);
+  }
+
+  void wide_chain(const Item &it, const ItemPlan &pl) {
+    const Group &g = it.g;
+    const Level &l = it.l;
+    const int C = it.C;
+    void *h = pl.fuse_mod ? it.f1 : it.f0, *y = pl.fuse_mod ? it.f0 : it.f1;
+    conv3(it, pl, g.conv1, it.x, h, g.gn1_g, g.gn1_b, nullptr, nullptr, nullptr);
+    conv3(it, pl, g.conv2, h, y, g.gn2_g, g.gn2_b, it.x, pl.fuse_mod ? rp_y() : nullptr, pl.fuse_mod ? &g.inject : nullptr);
+    if (pl.fuse_mod) return inject(it, pl, y);
+    timed("ln_modulate", 8.0 * l.rows * C, 2.0 * l.rows * C * dsize(u.dt),
+          [&] { SF_HIP(launch_ln_modulate(u.dt, y, C, p.mod_all + g.mod_off, p.mod_stride, 1e-6f, p.Bt, l.L, C, h, C, s,
+                                          pf_for(g.inject, (int)(l.rows / 4), l.rows))); });
+    inject(it, pl, h);
+  }
+
+  // Channel-block split-K chain (conv_cb.hip): the two launches that followed the convolutions anyway (GroupNorm+SiLU, LayerNorm +
+  // Modulation) sum the fp32 partial slabs; the second convolution applies GroupNorm+SiLU while staging its activation panel.
+  void cb_chain(const Item &it, const ItemPlan &pl) {
+    const Group &g = it.g;
+    const Level &l = it.l;
+    const int C = it.C, G = it.G, bt = p.Bt, kb = l.cb_kb, S = C / 128 / kb;
+    const double es = dsize(u.dt), rc = (double)l.rows * C;
+    const double cflops = 2.0 * rc * 3 * C, cbytes = 2.0 * rc * es + 3.0 * C * C * es;
+    const int mt = kb == 2 ? std::min(2, conv_cb_mt((int)l.rows, C, C / 2)) : conv_cb_mt((int)l.rows, C, C);
+    const int cwgs = (int)((l.rows + 32 * mt - 1) / (32 * mt)) * (C / 128) * S;
+    const CbGnPlan cgp = cb_gn_plan(l.L);
+    const int cbdt = u.x3 ? (int)F32X : u.dt;
+    ConvCbArgs a;
+    a.src_ld = C;
+    a.wp = g.conv1.wcb;
+    a.slab = p.cbslab;
+    a.B = bt;
+    a.L = l.L;
+    a.C = a.N = C;
+    a.kb = kb;
+    a.G = G;
+    a.eps = 1e-5f;
+    a.pf = pf_cb(g.conv2, cwgs);
+    if (gnpart_of == it.x && wants_gnpart(it.d)) {
+      // the GEMM that produced x left its GroupNorm tile statistics: GroupNorm+SiLU rides in conv1's panel prologue, no gn_silu launch
+      a.src = it.x;
+      a.pro = 2;
+      a.stats = p.gnpart;
+      a.gamma = g.gn1_g;
+      a.beta = g.gn1_b;
       timed("conv_cb", cflops + 12.0 * rc, cbytes, [&] { SF_HIP(launch_conv_cb(cbdt, a, s)); });
-      timed("cb_reduce_ln", 12.0 * rc, 3.0 * rc * es, [&] {
-        SF_HIP(launch_cb_reduce_ln(u.dt, p.cbslab, S, bt, l.L, C, g.conv2.bias, cur, C, p.mod_all + g.mod_off, p.mod_stride, 1e-6f, tA, C, s,
-                                   pf_for(g.inject, (int)(l.rows * (C / 4) / 256), l.rows)));
-      });
-      stats_of = nullptr;
-      ConvGemmArgs ai = inject_args(tA, tB);   // InjectChannels on the modulated rows (+ collapsed cross-attention bias when no attention follows)
-      if (fuse_attn) {
-        ai.rowpart_out = rp_z;
-        ai.rowpart_nt = C / 32;
-      }
-      if (g.attn) ai.pf = pf_for(g.qkv, (int)((l.rows + 31) / 32) * (C / 32), l.rows);
-      else if (next && arm_gnpart(g.inject, ai, d)) gnpart_of = tB;   // tB becomes `cur` below
-      conv(g.inject, ai, u.dt, u.dt);
-    } else if (use_cbd) {
-      // Direct channel-block chain (conv_cb.hip, ConvCbArgs::epi) at C = 128: the first convolution stores h and the GroupNorm chunk statistics of
-      // h, the second applies GroupNorm+SiLU from them while staging its panel and finishes + x, LayerNorm, Modulation in its epilogue; the plain
-      // InjectChannels GEMM follows.  Every launch hosts the weight prefetch of the next one.
-      const int bt = p.Bt;
-      const double es = dsize(u.dt), rc = (double)l.rows * C;
-      const double cflops = 2.0 * rc * 3 * C, cbytes = 2.0 * rc * es + 3.0 * C * C * es;
-      const int mt = std::min(2, conv_cb_mt((int)l.rows, C, C));
-      const int cwgs = (int)((l.rows + 32 * mt - 1) / (32 * mt));
+    } else {
       timed("gn_silu", 12.0 * rc, 3.0 * rc * es,
-            [&] { SF_HIP(launch_gn_silu(u.dt, cur, C, bt, l.L, C, G, g.gn1_g, g.gn1_b, 1e-5f, l.act, C, s, pf_cb(g.conv1, bt * G))); });
-      ConvCbArgs a;
+            [&] { SF_HIP(launch_gn_silu(u.dt, it.x, C, bt, l.L, C, G, g.gn1_g, g.gn1_b, 1e-5f, l.act, C, s, pf_cb(g.conv1, bt * G))); });
       a.src = l.act;
-      a.src_ld = C;
-      a.wp = g.conv1.wcb;
-      a.B = bt;
-      a.L = l.L;
-      a.C = a.N = C;
-      a.G = G;
-      a.eps = 1e-5f;
-      const CbGnPlan cgp = cb_gn_plan(l.L);   // the statistics chunks cb_reduce_gn would write
-      a.nch = cgp.nch;
-      a.chunk_rows = cgp.chunk_rows;
-      a.epi = 1;
-      a.out = tA;
-      a.out_ld = C;
-      a.bias = g.conv1.bias;
-      a.stats_out = p.slab;
-      a.pf = pf_cb(g.conv2, cwgs);
-      timed("conv_cb_gn", cflops + 6.0 * rc, cbytes, [&] { SF_HIP(launch_conv_cb(u.dt, a, s)); });
-      a.src = tA;
-      a.wp = g.conv2.wcb;
-      a.pro = 1;
-      a.stats = p.slab;
-      a.gamma = g.gn2_g;
-      a.beta = g.gn2_b;
-      a.epi = 2;
-      a.out = l.act;   // (the activated copy of x is dead: m takes its place, tB stays free for z)
-      a.bias = g.conv2.bias;
-      a.stats_out = nullptr;
-      a.res = cur;
-      a.res_ld = C;
-      a.ss = p.mod_all + g.mod_off;
-      a.ss_ld = p.mod_stride;
-      a.eps_ln = 1e-6f;
-      a.pf = pf_for(g.inject, cwgs, l.rows);
-      timed("conv_cb_ln", cflops + 24.0 * rc, cbytes + rc * es, [&] { SF_HIP(launch_conv_cb(u.dt, a, s)); });
-      stats_of = nullptr;
-      gnpart_of = nullptr;
-      ConvGemmArgs ai = inject_args(l.act, tB);   // InjectChannels on the modulated rows (+ collapsed cross-attention bias when no attention follows)
-      ai.short_k = 1;                             // K = 160: the 32x32 kernel the LayerNorm-folded form ran on, not the 64x64 tile
-      if (fuse_attn) {
-        ai.rowpart_out = rp_z;
-        ai.rowpart_nt = C / 32;
-      }
-      if (g.attn) ai.pf = pf_for(g.qkv, (int)((l.rows + 31) / 32) * (C / 32), l.rows);
-      conv(g.inject, ai, u.dt, u.dt);
-    } else {
-    conv3(g.conv1, cur, tA, g.gn1_g, g.gn1_b, nullptr, nullptr);
-    conv3(g.conv2, tA, tB, g.gn2_g, g.gn2_b, cur, fuse_mod ? rp_y : nullptr, fuse_mod ? &g.inject : nullptr);
-    if (fuse_mod) {
-      // Modulation + InjectChannels in one GEMM: m = LN_C(y; 1e-6) * (1 + scale) + shift;  z = m + Conv1x1(cat[m, ctx]) (+ bias)
-      ConvGemmArgs a = inject_args(tB, tA);
-      a.ln_part = rp_y;
-      a.ln_nt = C / 32;
-      a.ln_ss = p.mod_all + g.mod_off;
-      a.ln_ss_ld = p.mod_stride;
-      a.ln_eps = 1e-6f;
-      a.res_ln = 1;
-      if (fuse_attn) {
-        a.rowpart_out = rp_z;
-        a.rowpart_nt = C / 32;
-      }
-      if (g.attn) a.pf = pf_for(g.qkv, (int)((l.rows + 31) / 32) * (C / 32), l.rows);
-      conv(g.inject, a, u.dt, u.dt, /*ln=*/true);
-      std::swap(tA, tB);   // z -> tB, as the code below expects
-    } else {
-      // Modulation: LN_C(x; eps 1e-6) * (1 + scale) + shift
-      timed("ln_modulate", 8.0 * l.rows * C, 2.0 * l.rows * C * dsize(u.dt),
-            [&] { SF_HIP(launch_ln_modulate(u.dt, tB, C, p.mod_all + g.mod_off, p.mod_stride, 1e-6f, p.Bt, l.L, C, tA, C, s,
-                                            pf_for(g.inject, (int)(l.rows / 4), l.rows))); });
-      // InjectChannels: Conv1x1(cat[x, ctx]) + x   (+ collapsed cross-attention bias when no self-attention follows)
-      ConvGemmArgs a = inject_args(tA, tB);
-      if (fuse_attn) {
-        a.rowpart_out = rp_z;
-        a.rowpart_nt = C / 32;
-      }
-      if (g.attn) a.pf = pf_for(g.qkv, (int)((l.rows + 31) / 32) * (C / 32), l.rows);
-      conv(g.inject, a, u.dt, u.dt);
+      timed("conv_cb", cflops, cbytes, [&] { SF_HIP(launch_conv_cb(cbdt, a, s)); });
     }
-    }   // !use_cb
-    if (g.attn) {
-      // x + W_o MHA(W_q LN_a(x), W_kv LN_b(x)): the two LayerNorms share (mean, rstd); their affines are folded.
-      if (fuse_attn) {
-        ConvGemmArgs a = qkv_args(tB);
-        a.ln_part = rp_z;
-        a.ln_nt = C / 32;
-        a.ln_eps = 1e-5f;
-        a.ln_colsum = g.qkv_colsum;   // raw z through the MFMAs, rstd * (acc - mean * colsum) in the epilogue
-        a.pf = pf_for(g.attn_out, (int)((l.rows + 31) / 32) * (3 * u.hd / 32), l.rows);
-        conv(g.qkv, a, u.dt, u.dt, /*ln=*/true);
-      } else {
-        ConvGemmArgs aq = qkv_args(tA);
-        // fp32x on the macro tiles: the pre-norm's rows have no other reader and are written pre-split (kernels.h, ConvGemmArgs::src_x3)
-        const bool xf = u.x3 && (C % 32) == 0 && conv_gemm_src_x3_ok(filled(g.qkv, aq));
-        timed("ln_modulate", 6.0 * l.rows * C, 2.0 * l.rows * C * dsize(u.dt),
-              [&] { SF_HIP(launch_ln_modulate(u.dt, tB, C, nullptr, 0, 1e-5f, p.Bt, l.L, C, tA, C, s, Prefetch(), xf)); });
-        aq.src_x3 = xf ? 1 : 0;
-        conv(g.qkv, aq, u.dt, u.dt);
-      }
-      attention_tail(g, d, cur, tB, next);
-      u.dbg.tap(tapname, u.dt, cur, C, l.rows, C, s);
-      return;
+    gnpart_of = nullptr;
+    timed("cb_reduce_gn", 4.0 * rc, 2.0 * rc * es, [&] {
+      SF_HIP(launch_cb_reduce_gn(u.dt, p.cbslab, S, bt, l.L, C, g.conv1.bias, it.f0, C, G, p.slab, cgp, s, pf_cb(g.conv2, bt * cgp.nch * (C / 128))));
+    });
+    a.src = it.f0;
+    a.wp = g.conv2.wcb;
+    a.pro = 1;
+    a.nch = cgp.nch;
+    a.chunk_rows = cgp.chunk_rows;
+    a.stats = p.slab;
+    a.gamma = g.gn2_g;
+    a.beta = g.gn2_b;
+    a.pf = pf_for(g.inject, cwgs, l.rows);
+    timed("conv_cb", cflops + 12.0 * rc, cbytes, [&] { SF_HIP(launch_conv_cb(cbdt, a, s)); });
+    timed("cb_reduce_ln", 12.0 * rc, 3.0 * rc * es, [&] {
+      SF_HIP(launch_cb_reduce_ln(u.dt, p.cbslab, S, bt, l.L, C, g.conv2.bias, it.x, C, p.mod_all + g.mod_off, p.mod_stride, 1e-6f, it.f0, C, s,
+                                 pf_for(g.inject, (int)(l.rows * (C / 4) / 256), l.rows)));
+    });
+    stats_of = nullptr;
+    inject(it, pl, it.f0);   // on the modulated rows (m took h's place)
+  }
+
+  // Direct channel-block chain (conv_cb.hip, ConvCbArgs::epi) at C = 128: the first convolution stores h and the GroupNorm chunk statistics of
+  // h, the second applies GroupNorm+SiLU from them while staging its panel and finishes + x, LayerNorm, Modulation in its epilogue; the plain
+  // InjectChannels GEMM follows.  Every launch hosts the weight prefetch of the next one.
+  void cbd_chain(const Item &it, const ItemPlan &pl) {
+    const Group &g = it.g;
+    const Level &l = it.l;
+    const int C = it.C, G = it.G, bt = p.Bt;
+    const double es = dsize(u.dt), rc = (double)l.rows * C;
+    const double cflops = 2.0 * rc * 3 * C, cbytes = 2.0 * rc * es + 3.0 * C * C * es;
+    const int mt = std::min(2, conv_cb_mt((int)l.rows, C, C));
+    const int cwgs = (int)((l.rows + 32 * mt - 1) / (32 * mt));
+    timed("gn_silu", 12.0 * rc, 3.0 * rc * es,
+          [&] { SF_HIP(launch_gn_silu(u.dt, it.x, C, bt, l.L, C, G, g.gn1_g, g.gn1_b, 1e-5f, l.act, C, s, pf_cb(g.conv1, bt * G))); });
+    ConvCbArgs a;
+    a.src = l.act;
+    a.src_ld = C;
+    a.wp = g.conv1.wcb;
+    a.B = bt;
+    a.L = l.L;
+    a.C = a.N = C;
+    a.G = G;
+    a.eps = 1e-5f;
+    const CbGnPlan cgp = cb_gn_plan(l.L);   // the statistics chunks cb_reduce_gn would write
+    a.nch = cgp.nch;
+    a.chunk_rows = cgp.chunk_rows;
+    a.epi = 1;
+    a.out = it.f0;
+    a.out_ld = C;
+    a.bias = g.conv1.bias;
+    a.stats_out = p.slab;
+    a.pf = pf_cb(g.conv2, cwgs);
+    timed("conv_cb_gn", cflops + 6.0 * rc, cbytes, [&] { SF_HIP(launch_conv_cb(u.dt, a, s)); });
+    a.src = it.f0;
+    a.wp = g.conv2.wcb;
+    a.pro = 1;
+    a.stats = p.slab;
+    a.gamma = g.gn2_g;
+    a.beta = g.gn2_b;
+    a.epi = 2;
+    a.out = l.act;   // (the activated copy of x is dead: m takes its place, f1 stays free for z)
+    a.bias = g.conv2.bias;
+    a.stats_out = nullptr;
+    a.res = it.x;
+    a.res_ld = C;
+    a.ss = p.mod_all + g.mod_off;
+    a.ss_ld = p.mod_stride;
+    a.eps_ln = 1e-6f;
+    a.pf = pf_for(g.inject, cwgs, l.rows);
+    timed("conv_cb_ln", cflops + 24.0 * rc, cbytes + rc * es, [&] { SF_HIP(launch_conv_cb(u.dt, a, s)); });
+    stats_of = nullptr;
+    gnpart_of = nullptr;
+    inject(it, pl, l.act);
+  }
+
+  // x' = z + W_o MHA(W_q LN_a(z), W_kv LN_b(z)) (+ collapsed cross-attention bias) -> it.x, from z in it.f1
+  void self_attention(const Item &it, const ItemPlan &pl) {
+    const Group &g = it.g;
+    const Level &l = it.l;
+    const int C = it.C;
+    if (pl.fuse_attn) {
+      ConvGemmArgs a = qkv_args(it, it.f1, true);
+      a.pf = pf_for(g.attn_out, (int)((l.rows + 31) / 32) * (3 * u.hd / 32), l.rows);
+      conv(g.qkv, a, u.dt, u.dt, /*ln=*/true);
     } else {
-      void *o = cur;
-      cur = tB;
-      tB = tA;
-      tA = o;
-      u.dbg.tap(tapname, u.dt, cur, C, l.rows, C, s);
-      return;
-    }
-    }   // generic (non-thin) resnet / modulation / inject
-    if (g.attn) {
-      // thin level followed by self-attention: plain pre-norm launch
+      ConvGemmArgs a = qkv_args(it, it.f0, false);
+      // fp32x on the macro tiles: the pre-norm's rows have no other reader and are written pre-split (kernels.h, ConvGemmArgs::src_x3);
+      // a thin level's pre-norm stays plain
+      const bool xf = !pl.thin() && u.x3 && (C % 32) == 0 && conv_gemm_src_x3_ok(filled(g.qkv, a));
       timed("ln_modulate", 6.0 * l.rows * C, 2.0 * l.rows * C * dsize(u.dt),
-            [&] { SF_HIP(launch_ln_modulate(u.dt, tB, C, nullptr, 0, 1e-5f, p.Bt, l.L, C, tA, C, s)); });
-      {
-        ConvGemmArgs a;
-        a.src = tA;
-        a.src_ld = C;
-        a.M = (int)l.rows;
-        a.Lout = a.Lsrc = l.L;
-        a.out = l.qkv;
-        a.out_ld = 3 * u.hd;
-        conv(g.qkv, a, u.dt, u.dt);
-      }
-      attention_tail(g, d, cur, tB, next);
-      // result in cur's buffer; tA, tB free again
-    } else {
-      void *o = cur;
-      cur = tB;
-      tB = tA;
-      tA = o;
+            [&] { SF_HIP(launch_ln_modulate(u.dt, it.f1, C, nullptr, 0, 1e-5f, p.Bt, l.L, C, it.f0, C, s, Prefetch(), xf)); });
+      a.src_x3 = xf ? 1 : 0;
+      conv(g.qkv, a, u.dt, u.dt);
     }
-    u.dbg.tap(tapname, u.dt, cur, C, l.rows, C, s);
+    attention_tail(g, it.d, it.x, it.f1, it.next);
+  }
+
+  // cur is consumed; on return it names the buffer that holds the result and tB the other buffer that changed hands.  tA / tB: the two free buffers.
+  void group(const Group &g, int d, void *&cur, void *tA, void *&tB, const std::string &tapname, const Group *next = nullptr) {
+    const Item it = item_of(g, d, cur, tA, tB, next);
+    const ItemPlan pl = item_plan(g, d);
+    switch (pl.chain) {
+      case THIN: case THIN_TAIL: thin_chain(it, pl.chain == THIN_TAIL); break;
+      case WIDE: wide_chain(it, pl); break;
+      case CB: cb_chain(it, pl); break;
+      case CBD: cbd_chain(it, pl); break;
+    }
+    if (g.attn) self_attention(it, pl);   // z in tB -> the result in cur
+    else std::swap(cur, tB);              // z is the result
+    u.dbg.tap(tapname, u.dt, cur, it.C, it.l.rows, it.C, s);
   }
 
   // softmax attention on the packed q | k | v projections, then x' = z + W_o ao (+ collapsed cross-attention bias) -> `out`
@@ -1274,19 +1399,7 @@ struct Exec {
     const Level &l = p.lv[d];
     const int C = l.C;
     const size_t es = dsize(u.dt);
-    ConvGemmArgs a;
-    a.src = l.ao;
-    a.src_ld = u.hd;
-    a.M = (int)l.rows;
-    a.Lout = a.Lsrc = l.L;
-    a.out = out;
-    a.out_ld = C;
-    a.res = z;
-    a.res_ld = C;
-    if (g.cross) {
-      a.badd = p.ca_all + g.ca_off;
-      a.badd_ld = u.ca_ld;
-    }
+    ConvGemmArgs a = attn_out_args(g, d, out, z);
     // fp32x on the macro tiles: the attention kernel writes its output rows pre-split for the projection (the only reader)
     const bool xf = u.x3 && (u.hd % 32) == 0 && attention_f32_mfma_ok(3 * u.hd, 3 * u.hd, u.hd, p.Bt, u.cfg.attention_heads) &&
                     conv_gemm_src_x3_ok(filled(g.attn_out, a));
@@ -1301,153 +1414,6 @@ struct Exec {
       if (next->conv1.wcb) a.pf = pf_cb(next->conv1, (int)((l.rows + 31) / 32) * (C / 32));   // the next item starts with conv1 right away
     }
     conv(g.attn_out, a, u.dt, u.dt);
-  }
-
-  // Thin level (C = 32 / 64): the item is three conv_thin launches -- conv1 [GN+SiLU in, statistics of h out],
-  // conv2 [GN+SiLU in, + x], inject [LayerNorm-modulate in, + itself, (+ cross-attention bias), statistics out] --
-  // instead of gn_stats, conv, gn_stats, conv, ln_modulate, conv.  Returns false when the shape is not covered.
-  // On return: no attention -> result in cur; attention -> inject output in tB (what the attention code expects).
-  bool group_thin(const Group &g, int d, void *&cur, void *&tA, void *&tB) {
-    const Level &l = p.lv[d];
-    const Block &b = u.blocks[d];
-    const int C = l.C, G = u.cfg.resnet_groups;
-    if (g.conv1.cin != C || g.inject.cin != C) return false;
-    const void *w1 = g.conv1.direct ? g.conv1.wt : g.conv1.w, *w2 = g.conv2.direct ? g.conv2.wt : g.conv2.w;
-    const void *w3 = g.inject.direct ? g.inject.wt : g.inject.w;
-    if (!w1 || !w2 || !w3) return false;
-    const ThinPlan tp = conv_thin_plan(p.Bt, l.L, C);
-    ConvThinArgs base;
-    base.B = p.Bt;
-    base.L = base.Ls = l.L;
-    base.C = base.N = C;
-    base.G = G;
-    base.rw = tp.rw;
-    base.nchw = tp.nchw;
-    base.nch_in = tp.nchw;
-    base.chunk_in = tp.rw;
-    base.src_ld = base.out_ld = base.res_ld = C;
-    base.x3 = u.x3 ? 1 : 0;
-    ConvThinArgs a1 = base, a3 = base;
-    a1.taps = 3;
-    a1.pro = 1;
-    a3.taps = 1;
-    a3.pro = 2;
-    a3.C2 = g.inject.direct ? pad_to(g.inject.cin2, 8) : g.inject.cin2;
-    if (a3.C2 > b.ctx_ld) return false;
-    if (!conv_thin_supported(u.dt, a1) || !conv_thin_supported(u.dt, a3)) return false;
-    float *sA = p.slab, *sB = p.slab + p.slab_half;
-    const double es = dsize(u.dt), rc = (double)l.rows * C;
-    if (stats_of != cur)
-      timed("gn_stats", 3.0 * rc, rc * es, [&] { SF_HIP(launch_gn_stats(u.dt, cur, C, p.Bt, l.L, C, G, tp.nchw, tp.rw, sA, s)); });
-    {
-      ConvThinArgs a = a1;
-      a.src = cur;
-      a.w = w1;
-      if (g.conv1.direct) a.w32 = static_cast<const float *>(g.conv1.w);
-      a.bias = g.conv1.bias;
-      a.gamma = g.gn1_g;
-      a.beta = g.gn1_b;
-      a.stats_in = sA;
-      a.stats_out = sB;
-      a.out = tA;
-      timed("conv_thin", 2.0 * rc * 3 * C, 2.0 * rc * es + 3.0 * C * C * es, [&] { SF_HIP(launch_conv_thin(u.dt, a, s)); });
-    }
-    // conv2 + Modulation + InjectChannels in one launch when the fused tail covers the shape
-    {
-      ThinTailArgs t;
-      t.x3 = u.x3 ? 1 : 0;
-      t.h = tA;
-      t.x = cur;
-      t.ctx = l.ctx;
-      t.ctx_ld = b.ctx_ld;
-      t.w2 = w2;
-      if (g.conv2.direct && g.inject.direct) {
-        t.w2_32 = static_cast<const float *>(g.conv2.w);
-        t.w3_32 = static_cast<const float *>(g.inject.w);
-        t.c2real = g.inject.cin2;
-      }
-      t.bias2 = g.conv2.bias;
-      t.gamma = g.gn2_g;
-      t.beta = g.gn2_b;
-      t.stats_in = sB;
-      t.w3 = w3;
-      t.bias3 = g.inject.bias;
-      t.ss = p.mod_all + g.mod_off;
-      t.ss_ld = p.mod_stride;
-      if (g.cross && !g.attn) {
-        t.badd = p.ca_all + g.ca_off;
-        t.badd_ld = u.ca_ld;
-      }
-      t.out = tB;
-      t.stats_out = g.attn ? nullptr : sA;
-      t.B = p.Bt;
-      t.L = l.L;
-      t.C = C;
-      t.C2 = a3.C2;
-      t.G = G;
-      t.nch_in = tp.nchw;
-      t.chunk_in = tp.rw;
-      t.rw = tp.rw;
-      t.nchw = tp.nchw;
-      if (!u.no_thin_tail && g.conv2.bias && g.inject.bias && thin_tail_supported(u.dt, t)) {
-        const double kin = g.inject.kreal > 0 ? g.inject.kreal : g.inject.K;
-        timed("conv_thin", 2.0 * rc * 3 * C + 2.0 * rc * kin + 8.0 * rc, 3.0 * rc * es + (double)l.rows * (kin - C) * es + (3.0 * C + kin) * C * es,
-              [&] { SF_HIP(launch_thin_tail(u.dt, t, s)); });
-        if (g.attn) {
-          stats_of = nullptr;   // z in tB, tA free: what the attention code expects
-        } else {
-          void *o = cur;
-          cur = tB;
-          tB = o;
-          stats_of = cur;
-        }
-        return true;
-      }
-    }
-    {
-      ConvThinArgs a = a1;
-      a.src = tA;
-      a.w = w2;
-      if (g.conv2.direct) a.w32 = static_cast<const float *>(g.conv2.w);
-      a.bias = g.conv2.bias;
-      a.gamma = g.gn2_g;
-      a.beta = g.gn2_b;
-      a.stats_in = sB;
-      a.res = cur;
-      a.out = tB;
-      timed("conv_thin", 2.0 * rc * 3 * C, 3.0 * rc * es + 3.0 * C * C * es, [&] { SF_HIP(launch_conv_thin(u.dt, a, s)); });
-    }
-    {
-      ConvThinArgs a = a3;
-      a.src = tB;
-      a.src2 = l.ctx;
-      a.src2_ld = b.ctx_ld;
-      a.w = w3;
-      a.bias = g.inject.bias;
-      a.ss = p.mod_all + g.mod_off;
-      a.ss_ld = p.mod_stride;
-      a.eps = 1e-6f;
-      a.res_self = 1;
-      if (g.cross && !g.attn) {
-        a.badd = p.ca_all + g.ca_off;
-        a.badd_ld = u.ca_ld;
-      }
-      a.stats_out = g.attn ? nullptr : sA;
-      a.out = tA;
-      const double kin = g.inject.kreal > 0 ? g.inject.kreal : g.inject.K;
-      timed("conv_thin", 2.0 * rc * kin + 8.0 * rc, 2.0 * rc * es + (double)l.rows * (kin - C) * es + kin * C * es,
-            [&] { SF_HIP(launch_conv_thin(u.dt, a, s)); });
-    }
-    if (g.attn) {
-      std::swap(tA, tB);   // inject output -> tB, tA free
-      stats_of = nullptr;
-    } else {
-      void *o = cur;
-      cur = tA;
-      tA = o;
-      stats_of = cur;
-    }
-    return true;
   }
 
   // Block d: skip + scale * Up(items_up(inner(items_down(Down(x)))))
