@@ -725,6 +725,59 @@ int64_t sf_clap_audio_workspace_bytes(const sf_clap_audio *h, int B);
 int sf_clap_audio_forward(sf_clap_audio *h, const float *image, int B, float *embedding, float *const *taps, void *ws, int64_t ws_bytes, void *stream);
 int sf_clap_audio_describe(const sf_clap_audio_config *cfg, int B, char *text /*host*/, int64_t capacity);
 
+/* ------------------------------------------------------------------------------------------
+ * CLAP text embedder (syncfusion_amd/clap_text.py)
+ *   replaces: laion_clap.CLAP_Module(...).get_text_embedding(text, use_tensor=True)
+ *   (main/module_diffusion.py:69-71; the text-conditioned generation of exp/evaluate_gh_gen_text.yaml:29, cond_text: True): RoBERTa
+ *   (post-LN encoder, key-padding mask, pooler) and a two-layer projection on token ids.  Tokenisation is the caller's (host).  ids and
+ *   mask are int32 (B, S), contiguous, on the device; everything else fp32; fp32 MFMA GEMMs, fp32 accumulation.
+ *
+ * sf_op_text_embed   ids (B, S) -> out (B S, C): LayerNorm_C(word[id] + pos[p] + type[:]; gamma, beta), p = pad_id + (the number of
+ *     ids != pad_id in the row up to and including this column) for a real token and pad_id for a pad.  One wave per row, two-pass
+ *     statistics.  id and p are clamped into their tables (vocab, n_pos rows): memory safety only.  Refused before any HIP call: null
+ *     pointers, B, S, vocab, n_pos < 1, eps <= 0 (SF_ERR_INVALID); C no multiple of 64 or above 1024 (SF_ERR_UNSUPPORTED); 2^31 elements
+ *     or more (SF_ERR_SHAPE).
+ * sf_op_layernorm_affine   y = LN_C(x) gamma + beta on `rows` rows, one wave per row, two passes.  Refusals as above.
+ * sf_op_masked_attention   qkv (B S, 3 C) rows, columns [q | k | v] each (heads, 64), C = 64 heads; mask (B, S), non-zero = a real
+ *     token -> out (B S, C): softmax(q k^T / 8) v over the keys the mask admits.  A masked key carries weight exactly 0 and its K and V
+ *     rows never enter the arithmetic (they may hold anything); masked QUERY rows are computed like any other; a text whose mask admits no
+ *     key gives zeros.  One workgroup per (text, head), fixed-order sums: a text's rows do not depend on the batch.  Refused before any
+ *     HIP call: null pointers, B, S, heads < 1 (SF_ERR_INVALID); S > 128 (SF_ERR_UNSUPPORTED); 2^31 elements or more (SF_ERR_SHAPE).
+ * sf_clap_text_create   the network.  Named weights (DEVICE pointers, copied before the call returns):
+ *       emb.word (vocab, C)  emb.pos (max_positions, C)  emb.type (C)  emb.g  emb.beta
+ *       l{i}.qkv.w (3 C, C)  .qkv.b (3 C)          query | key | value concatenated by the caller
+ *       l{i}.ao.w (C, C)  .ao.b  .ln1.g  .ln1.beta  the attention output and the LayerNorm behind its residual add
+ *       l{i}.fc1.w (I, C)  .fc1.b  .fc2.w (C, I)  .fc2.b  .ln2.g  .ln2.beta
+ *       pool.w (C, C)  pool.b                       pooling == 0 only
+ *       proj0.w (J, C)  proj0.b  proj2.w (J, J)  proj2.b
+ *     Refused before any HIP call: null pointers, counts out of range (SF_ERR_INVALID); hidden != 64 heads, hidden above 1024,
+ *     max_length above 128 (SF_ERR_UNSUPPORTED); max_length + pad_id + 1 above max_positions, joint_dim above 1024 (SF_ERR_SHAPE); a
+ *     missing or mis-sized weight (SF_ERR_MISSING_WEIGHT, named).
+ * sf_clap_text_workspace_bytes   the workspace of B texts of S columns (-1 out of range).
+ * sf_clap_text_forward   ids, mask (B, S) -> embedding (B, joint_dim).  taps: NULL, or layers + 2 device pointers (each may be NULL) that
+ *     receive the (B S, C) hidden state behind the embeddings and behind every layer, and the (B, C) pooled rows, for tests.  Refused
+ *     before any HIP call: null pointers, B or S < 1 (SF_ERR_INVALID); S above 128 (SF_ERR_UNSUPPORTED); S above max_length or the
+ *     position table, too many rows (SF_ERR_SHAPE); a workspace below the query (SF_ERR_WORKSPACE); a GEMM shape no kernel takes
+ *     (SF_ERR_UNSUPPORTED).  Nothing is allocated and nothing synchronises.
+ * sf_clap_text_describe   HOST-only: one line per GEMM of a layer at (B, S) with the kernel family the dispatcher gives it. */
+typedef struct {
+  int32_t vocab_size, hidden, layers, heads, intermediate, max_positions, pad_id, max_length, joint_dim;
+  float ln_eps;
+  int32_t pooling; /* 0: tanh(Linear) of token 0 (pooler_output); 1: token 0 as it is */
+  int32_t projection_relu, normalize;
+} sf_clap_text_config;
+typedef struct sf_clap_text sf_clap_text;
+int sf_op_text_embed(const int32_t *ids, int B, int S, int C, int vocab, int n_pos, int pad_id, const float *word, const float *pos, const float *type,
+                     const float *gamma, const float *beta, float eps, float *out, void *stream);
+int sf_op_layernorm_affine(const float *x, int64_t rows, int C, const float *gamma, const float *beta, float eps, float *y, void *stream);
+int sf_op_masked_attention(const float *qkv, const int32_t *mask, int B, int S, int heads, float *out, void *stream);
+int sf_clap_text_create(const sf_clap_text_config *cfg, const sf_tensor *weights, int n_weights, void *stream, sf_clap_text **out);
+void sf_clap_text_destroy(sf_clap_text *h);
+int64_t sf_clap_text_workspace_bytes(const sf_clap_text *h, int B, int S);
+int sf_clap_text_forward(sf_clap_text *h, const int32_t *ids, const int32_t *mask, int B, int S, float *embedding, float *const *taps, void *ws,
+                         int64_t ws_bytes, void *stream);
+int sf_clap_text_describe(const sf_clap_text_config *cfg, int B, int S, char *text /*host*/, int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,12 @@ class ClapAudioEngineConfig(C.Structure):
                 ("ln_eps", C.c_float), ("mask_value", C.c_float), ("projection_relu", C.c_int32), ("normalize", C.c_int32)]
 
 
+class ClapTextEngineConfig(C.Structure):
+    """sf_clap_text_config: RoBERTa and the projection behind the token ids (syncfusion_amd/clap_text.py)."""
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "hidden", "layers", "heads", "intermediate", "max_positions", "pad_id", "max_length", "joint_dim")] + \
+               [("ln_eps", C.c_float), ("pooling", C.c_int32), ("projection_relu", C.c_int32), ("normalize", C.c_int32)]
+
+
 # every symbol include/syncfusion_amd.h declares: (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -239,6 +245,21 @@ SYMBOLS = {
     "sf_clap_audio_forward": (_I, [_P, _P, _I, _P, _P, _P, _L, _P]),
     # (cfg, B, text_host, capacity)
     "sf_clap_audio_describe": (_I, [C.POINTER(ClapAudioEngineConfig), _I, C.c_char_p, _L]),
+    # the CLAP text embedder (syncfusion_amd/clap_text.py)
+    # (ids, B, S, C, vocab, n_pos, pad_id, word, pos, type, gamma, beta, eps, out, stream)
+    "sf_op_text_embed": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P]),
+    # (x, rows, C, gamma, beta, eps, y, stream)
+    "sf_op_layernorm_affine": (_I, [_P, _L, _I, _P, _P, _F, _P, _P]),
+    # (qkv, mask, B, S, heads, out, stream)
+    "sf_op_masked_attention": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    # (cfg, weights, n_weights, stream, out)
+    "sf_clap_text_create": (_I, [C.POINTER(ClapTextEngineConfig), C.POINTER(SfTensor), _I, _P, C.POINTER(_P)]),
+    "sf_clap_text_destroy": (None, [_P]),
+    "sf_clap_text_workspace_bytes": (_L, [_P, _I, _I]),
+    # (h, ids, mask, B, S, embedding, taps, ws, ws_bytes, stream)
+    "sf_clap_text_forward": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _L, _P]),
+    # (cfg, B, S, text_host, capacity)
+    "sf_clap_text_describe": (_I, [C.POINTER(ClapTextEngineConfig), _I, _I, C.c_char_p, _L]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -5,7 +5,8 @@ uses it: ``load_ckpt`` and ``get_audio_embedding_from_data(x, use_tensor=True)``
 ``laion_clap`` nor ``transformers``, ``torchlibrosa`` or ``timm`` is needed.  The mel power comes from the FFT front end
 (``csrc/audio_features.hip``); the log / BatchNorm / bicubic / fold pass, the patch embed and the embedding tail run in
 ``csrc/clap_front.hip``, shifted-window attention and the LayerNorms in ``csrc/swin.hip``, every Linear on the library's fp32
-implicit-GEMM launcher (``csrc/clap_engine.cpp``).  The text branch (RoBERTa) is not built.  Weights come from a file the user supplies;
+implicit-GEMM launcher (``csrc/clap_engine.cpp``).  The text branch (RoBERTa) lives in ``clap_text.py`` (``ClapEmbedder``, a subclass that
+adds it); this class keeps refusing text.  Weights come from a file the user supplies;
 nothing is ever fetched.  The default ``config.TARGET_MAP`` still sends ``laion_clap.CLAP_Module`` to the offline stub; opt in with
 ``_target_: syncfusion_amd.clap.ClapAudioEmbedder`` or ``instantiate(cfg, embedder=ClapAudioEmbedder(), embedder_checkpoint=...)``.
 
@@ -214,18 +215,22 @@ class _ClapModel(nn.Module):
         self.audio_projection = nn.Sequential(nn.Linear(cfg.final_dim, cfg.joint_dim), nn.ReLU(), nn.Linear(cfg.joint_dim, cfg.joint_dim))
 
 
-def normalise_keys(state: Dict[str, Tensor]) -> Dict[str, Tensor]:
-    """An upstream / Lightning / SyncFusion state dict -> ``{"model.audio_branch.*" | "model.audio_projection.*": tensor}``: the prefixes
-    ``module.``, ``clap.``, ``model.`` are stripped in any combination; the text branch, ``logit_scale_*``, ``audio_transform.*``,
-    ``text_*``, the STFT convolutions, ``tscam_conv.*``, ``head.*``, ``attn_mask`` and ``relative_position_index`` are dropped."""
+AUDIO_PARTS = ("audio_branch.", "audio_projection.")
+
+
+def normalise_keys(state: Dict[str, Tensor], parts: Tuple[str, ...] = AUDIO_PARTS, ignored: Tuple[str, ...] = IGNORED_PARTS) -> Dict[str, Tensor]:
+    """An upstream / Lightning / SyncFusion state dict -> ``{"model.<part>*": tensor}`` for the ``parts`` a class reads (the audio class:
+    ``audio_branch.``, ``audio_projection.``): the prefixes ``module.``, ``clap.``, ``model.`` are stripped in any combination; everything
+    else (for the audio class the text branch and ``text_*``; ``logit_scale_*``, ``audio_transform.*``) and, inside the parts, whatever
+    holds one of ``ignored`` (the STFT convolutions, ``tscam_conv.*``, ``attn_mask``, ``relative_position_index``) and ``head.*`` are dropped."""
     out: Dict[str, Tensor] = {}
     for k, v in state.items():
         key = k
         while key.startswith(KEY_PREFIXES):
             key = key[len(next(p for p in KEY_PREFIXES if key.startswith(p))):]
-        if not key.startswith(("audio_branch.", "audio_projection.")):
+        if not key.startswith(parts):
             continue
-        if key.startswith("audio_branch.head.") or any(part in key for part in IGNORED_PARTS):
+        if key.startswith("audio_branch.head.") or any(part in key for part in ignored):
             continue
         out["model." + key] = v
     return out
@@ -237,12 +242,16 @@ class ClapAudioEmbedder(nn.Module):
     (``load_ckpt``, ``load_state_dict``, a parent's ``load_state_dict``) and every ``.to()`` drops it, and the next call builds it again;
     after editing a parameter in place call ``invalidate()``."""
 
+    # what load_state_dict keeps of a checkpoint: the parts this class owns, minus the keys that hold one of IGNORED (a subclass extends both)
+    PARTS: Tuple[str, ...] = AUDIO_PARTS
+    IGNORED: Tuple[str, ...] = IGNORED_PARTS
+
     def __init__(self, config: Optional[ClapAudioConfig] = None, enable_fusion: bool = False, amodel: str = "HTSAT-tiny", **_ignored):
         super().__init__()
         if enable_fusion:
-            raise ValueError("ClapAudioEmbedder: enable_fusion=True (the fusion model) is not built")
+            raise ValueError(f"{type(self).__name__}: enable_fusion=True (the fusion model) is not built")
         if amodel != "HTSAT-tiny":
-            raise ValueError(f"ClapAudioEmbedder: amodel {amodel!r} is not built, only 'HTSAT-tiny'")
+            raise ValueError(f"{type(self).__name__}: amodel {amodel!r} is not built, only 'HTSAT-tiny'")
         self.config = config = ClapAudioConfig() if config is None else config
         config.check()
         with torch.random.fork_rng(devices=[]):
@@ -293,14 +302,14 @@ class ClapAudioEmbedder(nn.Module):
         """Upstream's keys under any of the known prefixes; what the audio path does not read is dropped, ``logmel_extractor.melW`` is
         optional, a missing key or a shape mismatch in the rest raises and names the key."""
         own = super().state_dict()
-        state = normalise_keys(state_dict)
+        state = normalise_keys(state_dict, self.PARTS, self.IGNORED)
         for k in OPTIONAL_KEYS:
             state.setdefault(k, own[k])
         for k, v in own.items():
             if k not in state:
-                raise KeyError(f"ClapAudioEmbedder: the checkpoint has no '{k[len('model.'):]}'")
+                raise KeyError(f"{type(self).__name__}: the checkpoint has no '{k[len('model.'):]}'")
             if tuple(state[k].shape) != tuple(v.shape):
-                raise ValueError(f"ClapAudioEmbedder: '{k[len('model.'):]}' has shape {tuple(state[k].shape)}, expected {tuple(v.shape)}")
+                raise ValueError(f"{type(self).__name__}: '{k[len('model.'):]}' has shape {tuple(state[k].shape)}, expected {tuple(v.shape)}")
         self.invalidate()
         return super().load_state_dict({k: state[k] for k in own}, strict=True, **kwargs)
 
@@ -486,4 +495,4 @@ class ClapAudioEmbedder(nn.Module):
         return self.embed_image(self.logmel_image(self.mel_power(wav)))
 
     def get_text_embedding(self, *args, **kwargs):
-        raise NotImplementedError("ClapAudioEmbedder: the text branch (RoBERTa) is not built; only get_audio_embedding_from_data is")
+        raise NotImplementedError("ClapAudioEmbedder: the audio side only, no text branch (RoBERTa); syncfusion_amd.ClapEmbedder has both")

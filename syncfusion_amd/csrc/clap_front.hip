@@ -140,10 +140,12 @@ __global__ __launch_bounds__(TAIL_THREADS) void clap_pool_kernel(const float *__
   }
 }
 
-// y[b][n] = act(sum_k w[n][k] x[b][k] + bias[n]) for a handful of rows b: one wave per output n, its weight row in the lanes' registers
-// (read once for every clip), wave-level sums in a fixed order: a clip's outputs do not depend on the batch.  K <= 1024
-__global__ __launch_bounds__(LIN_WAVES *WAVE) void clap_linear_kernel(const float *__restrict__ x, int B, int K, int N, const float *__restrict__ w,
-                                                                      const float *__restrict__ bias, int relu, float *__restrict__ y) {
+// y[b][n] = act(sum_k w[n][k] x[b x_ld + k] + bias[n]) for a handful of rows b: one wave per output n, its weight row in the lanes'
+// registers (read once for every clip), wave-level sums in a fixed order: a clip's outputs do not depend on the batch.  K <= 1024.
+// act: CLAP_ACT_NONE, CLAP_ACT_RELU, CLAP_ACT_TANH
+__global__ __launch_bounds__(LIN_WAVES *WAVE) void clap_linear_kernel(const float *__restrict__ x, int64_t x_ld, int B, int K, int N,
+                                                                      const float *__restrict__ w, const float *__restrict__ bias, int act,
+                                                                      float *__restrict__ y) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int n = blockIdx.x * LIN_WAVES + (threadIdx.x >> 6);
   if (n >= N) return;
@@ -153,13 +155,13 @@ __global__ __launch_bounds__(LIN_WAVES *WAVE) void clap_linear_kernel(const floa
   for (int j = 0; j < LIN_MAXV; ++j) wv[j] = j * WAVE + lane < K ? wr[j * WAVE + lane] : 0.f;
   const float bn = bias[n];
   for (int b = 0; b < B; ++b) {
-    const float *xr = x + (int64_t)b * K;
+    const float *xr = x + (int64_t)b * x_ld;
     float a = 0.f;
 #pragma unroll
     for (int j = 0; j < LIN_MAXV; ++j)
       if (j * WAVE + lane < K) a = fmaf(wv[j], xr[j * WAVE + lane], a);
     a = wave_sum(a) + bn;
-    if (lane == 0) y[(int64_t)b * N + n] = relu ? fmaxf(a, 0.f) : a;
+    if (lane == 0) y[(int64_t)b * N + n] = act == CLAP_ACT_RELU ? fmaxf(a, 0.f) : act == CLAP_ACT_TANH ? tanhf(a) : a;
   }
 }
 
@@ -201,10 +203,23 @@ hipError_t launch_clap_tail(const float *x, int B, int ntok, int C, int J, const
                             const float *b1, const float *w2, const float *b2, int relu, int normalize, float *scratch, float *out, hipStream_t s) {
   if (B < 1 || ntok < 1 || ntok > TAIL_MAXTOK || C < 1 || C > TAIL_MAXC || J < 1 || J > TAIL_MAXJ || !scratch) return hipErrorInvalidValue;
   float *pooled = scratch, *hid = pooled + (int64_t)B * C, *emb = hid + (int64_t)B * J;
-  const dim3 lin_grid((J + LIN_WAVES - 1) / LIN_WAVES), lin_block(LIN_WAVES * WAVE);
   hipLaunchKernelGGL(clap_pool_kernel, dim3(B), dim3(TAIL_THREADS), 0, s, x, ntok, C, gamma, beta, eps, pooled);
-  hipLaunchKernelGGL(clap_linear_kernel, lin_grid, lin_block, 0, s, pooled, B, C, J, w1, b1, relu, hid);
-  hipLaunchKernelGGL(clap_linear_kernel, lin_grid, lin_block, 0, s, hid, B, J, J, w2, b2, 0, emb);
+  return launch_clap_projection(pooled, B, C, J, w1, b1, relu, w2, b2, normalize, hid, emb, out, s);
+}
+
+hipError_t launch_clap_linear(const float *x, int64_t x_ld, int B, int K, int N, const float *w, const float *bias, int act, float *y, hipStream_t s) {
+  if (B < 1 || K < 1 || K > LIN_MAXV * WAVE || N < 1 || x_ld < K) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(clap_linear_kernel, dim3((N + LIN_WAVES - 1) / LIN_WAVES), dim3(LIN_WAVES * WAVE), 0, s, x, x_ld, B, K, N, w, bias, act, y);
+  return hipGetLastError();
+}
+
+hipError_t launch_clap_projection(const float *pooled, int B, int C, int J, const float *w1, const float *b1, int relu, const float *w2,
+                                  const float *b2, int normalize, float *hid, float *emb, float *out, hipStream_t s) {
+  if (B < 1 || C < 1 || C > TAIL_MAXC || J < 1 || J > TAIL_MAXJ) return hipErrorInvalidValue;
+  hipError_t e = launch_clap_linear(pooled, C, B, C, J, w1, b1, relu ? CLAP_ACT_RELU : CLAP_ACT_NONE, hid, s);
+  if (e != hipSuccess) return e;
+  e = launch_clap_linear(hid, J, B, J, J, w2, b2, CLAP_ACT_NONE, emb, s);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(clap_l2norm_kernel, dim3(B), dim3(WAVE), 0, s, emb, J, normalize, out);
   return hipGetLastError();
 }
