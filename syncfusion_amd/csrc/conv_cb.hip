@@ -85,7 +85,13 @@ __device__ __forceinline__ float2 merge_parts(const float2 (&cs)[4], const float
 //                  MFMA loop) in cb_reduce_ln's summation order; LayerNorm + Modulation -> 16-bit, the chain's m bit for bit.
 // Their operands (bias, residual rows, scale / shift of the tile's clip) are requested behind the weight loads.
 template <typename T, int MT, bool PRO, int KB, int EPI = 0>
-__global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const int mtiles, const unsigned bytes_src) {
+__global__ __launch_bounds__(256) void conv_cb_kernel(const void *const src, const void *const wimg, const unsigned bytes_src, const int mtiles, const int M,
+                                                      const int L, const unsigned magicL, const int src_ld, const int N, const unsigned lg,
+                                                      const ConvCbArgs a) {
+  // argument head (12 dwords, preloaded into SGPRs with the wave: kernels.h, "argument heads"): what the prefetch test, the tile index, the
+  // panel loads and the weight-fragment loads need (lg = log2S | log2cpg << 8).  `a` arrives through scalar loads behind them; the head
+  // fields are NOT read from it here.
+  const int log2S = (int)(lg & 255u), log2cpg = (int)(lg >> 8);
   using frag = typename Frag16<T>::type;
   using v4 = T __attribute__((ext_vector_type(4)));
   static_assert(EPI == 0 || (KB == 1 && MT <= 2), "direct epilogues: one channel block, at most two row tiles");
@@ -102,15 +108,15 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   }
   // workgroups that share a weight slice (same x) are nws apart in dispatch order: with nws % 8 == 0 they land on the same XCD
   const int mt = (int)blockIdx.y, ws = (int)blockIdx.x;
-  const int nt = ws >> a.log2S, cb = ws & ((1 << a.log2S) - 1);
-  const int r0 = mt * BM, M = a.B * a.L;
-  auto divL = [&](int x) { return (int)__umulhi((unsigned)x, a.magicL); };
+  const int nt = ws >> log2S, cb = ws & ((1 << log2S) - 1);
+  const int r0 = mt * BM;
+  auto divL = [&](int x) { return (int)__umulhi((unsigned)x, magicL); };
 
   // ---- 1. activation panel: rows r0 - 1 .. r0 + BM of channel block cb (16 threads per row, 16 rows per pass) ----------------
-  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.src), 0, bytes_src, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(src), 0, bytes_src, 0x00020000);
   const int cv = tid % TPR, pr = tid / TPR;
   Vec16<T> pv[NV];
-  const unsigned col_b = (unsigned)((cb * KCW + cv * 8) * sizeof(T)), row_b = (unsigned)(a.src_ld * sizeof(T));
+  const unsigned col_b = (unsigned)((cb * KCW + cv * 8) * sizeof(T)), row_b = (unsigned)(src_ld * sizeof(T));
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int j = pr + RPP * i, r = r0 - 1 + j;
@@ -120,7 +126,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   // ---- 2. GroupNorm operands: gamma / beta of this thread's channel octet, chunk statistics of the clips the panel touches ----------
   //         (8 lanes per (clip, group) pair, 4 chunks each; every address is clamped so that the loads are branch-free and all in
   //         flight together, behind the panel loads and in front of the weight loads: the first wait must not cover the weights)
-  const int gshift = KC_LOG2 + (KB == 2 ? 1 : 0) - a.log2cpg;   // log2(groups inside the workgroup's channel range)
+  const int gshift = KC_LOG2 + (KB == 2 ? 1 : 0) - log2cpg;   // log2(groups inside the workgroup's channel range)
   const int clip0 = divL(max(r0 - 1, 0));
   const int nclip = PRO ? (divL(min(r0 + BM, M - 1)) - clip0 + 1) : 0;
   const int npair = nclip << gshift;                           // <= NSLOT * 8 = 32: one pair per 8 lanes
@@ -131,7 +137,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   int lim[NRD] = {0};
   const int sub = tid & 7;
   if constexpr (PRO) {
-    const int G = a.C >> a.log2cpg;
+    const int G = a.C >> log2cpg;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       ga[q] = *reinterpret_cast<const f32x4 *>(a.gamma + cb * KCW + cv * 8 + 4 * q);
@@ -140,13 +146,13 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
     // pro 1: chunk (mean, M2) [clip][nch][G]; pro 2: tile (mean, M2) [m tile][C / 32][segment] of the producing GEMM (kernels.h).  One address
     // select per load instead of two code paths: loaded values that meet at a join cost a wait in front of the weight loads.
     const bool tiles = a.pro == 2;
-    const int ltpg = a.log2cpg - 5, ct = a.C >> 5;               // log2(32-column tiles per group), tiles per row
+    const int ltpg = log2cpg - 5, ct = a.C >> 5;               // log2(32-column tiles per group), tiles per row
 #pragma unroll
     for (int rd = 0; rd < NRD; ++rd) {
       const int p = min((tid >> 3) + 32 * rd, npair - 1);
       const int slot = p >> gshift, gi = p & ((1 << gshift) - 1);
       const int clip = clip0 + slot;
-      const int mt_lo = (clip * a.L) >> 5, nmt = ((clip * a.L + a.L - 1) >> 5) - mt_lo + 1;
+      const int mt_lo = (clip * L) >> 5, nmt = ((clip * L + L - 1) >> 5) - mt_lo + 1;
       lim[rd] = tiles ? (nmt << max(ltpg, 0)) : a.nch;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
         const unsigned off2 = (unsigned)(((mtile * ct + tile) * 2 + (clip - divL(mtile << 5))) * 2);
         const unsigned off1 = (unsigned)((((clip * a.nch + kc) * G) + (cb << gshift) + gi) * 2);
         cs[rd][k] = *reinterpret_cast<const float2 *>(a.stats + (tiles ? off2 : off1));
-        cn[rd][k] = part_count(tiles, clip, kc, mtile, a.L, a.chunk_rows, a.log2cpg);
+        cn[rd][k] = part_count(tiles, clip, kc, mtile, L, a.chunk_rows, log2cpg);
       }
     }
   }
@@ -165,7 +171,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   frag wf[24 * KB];
 #pragma unroll
   for (int blk = 0; blk < KB; ++blk) {
-    const frag *wp = reinterpret_cast<const frag *>(a.wp) + ((size_t)((cb * KB + blk) * (a.N >> 5) + (nt * 4 + wave)) * 24) * 64;   // uniform
+    const frag *wp = reinterpret_cast<const frag *>(wimg) + ((size_t)((cb * KB + blk) * (N >> 5) + (nt * 4 + wave)) * 24) * 64;   // uniform
 #pragma unroll
     for (int s = 0; s < 24; ++s) wf[blk * 24 + s] = wp[s * 64 + lane];
   }
@@ -182,7 +188,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   }
   if constexpr (EPI == 2) {
     const float *ssp = a.ss ? a.ss : a.bias;
-    const int sh_off = a.ss ? a.N : 0;
+    const int sh_off = a.ss ? N : 0;
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
       const int m = min(r0 + t * 32 + fr, M - 1);
@@ -206,7 +212,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   }
   // ---- 4. statistics of the touched (clip, group) pairs -> LDS ----------------------------------------------------------------
   if constexpr (PRO) {
-    const float rn = 1.0f / ((float)a.L * (float)(1 << a.log2cpg));
+    const float rn = 1.0f / ((float)L * (float)(1 << log2cpg));
 #pragma unroll
     for (int rd = 0; rd < NRD; ++rd) {
       const float2 st = merge_parts(cs[rd], cn[rd], sub, lim[rd], rn, a.eps);
@@ -222,7 +228,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
     if (j < PR) {
       Vec16<T> o = pv[i];
       if (PRO && r >= 0 && r < M) {
-        const float2 st = gstat[divL(r) - clip0][(cv * 8) >> a.log2cpg];
+        const float2 st = gstat[divL(r) - clip0][(cv * 8) >> log2cpg];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float sc = st.y * ga[e >> 2][e & 3];
@@ -239,9 +245,9 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   bool ok0[MT], ok2[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
-    const int m = r0 + t * 32 + fr, l = m - divL(m) * a.L;
+    const int m = r0 + t * 32 + fr, l = m - divL(m) * L;
     ok0[t] = l > 0;              // tap 0 reads position l - 1 of the same clip
-    ok2[t] = l < a.L - 1;        // tap 2 reads position l + 1
+    ok2[t] = l < L - 1;        // tap 2 reads position l + 1
   }
   f32x16 acc[MT];
 #pragma unroll
@@ -264,7 +270,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
         }
   if constexpr (EPI == 0) {
   // ---- 7. partial slab ---------------------------------------------------------------------------------------------------------
-  float *sl = a.slab + (size_t)cb * M * a.N + nt * 128 + wave * 32 + 4 * fh;
+  float *sl = a.slab + (size_t)cb * M * N + nt * 128 + wave * 32 + 4 * fh;
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     const int m = r0 + t * 32 + fr;
@@ -272,7 +278,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         f32x4 v = {acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
-        *reinterpret_cast<f32x4 *>(sl + (unsigned)(m * a.N + 8 * g)) = v;
+        *reinterpret_cast<f32x4 *>(sl + (unsigned)(m * N + 8 * g)) = v;
       }
     }
   }
@@ -304,7 +310,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
   {
     const int R = a.chunk_rows, P = R >> 3;
     const int cq = tid & 31, rr = tid >> 5;            // thread = 4 consecutive columns of one row per pass, as in cb_reduce_gn
-    const int cpg = 1 << a.log2cpg, span = cpg >> 2, gpb = KC >> a.log2cpg;
+    const int cpg = 1 << log2cpg, span = cpg >> 2, gpb = KC >> log2cpg;
     auto group_total = [&](float tt, int k) {
       for (int off = 1; off < span; off <<= 1) tt += __shfl_xor(tt, off, 64);
       tt += __shfl_xor(tt, 32, 64);
@@ -347,7 +353,7 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
         }
       const float a2 = group_total(s2, 1);
       if (tid < gpb && m0 < M) {
-        const int clip = divL(m0), kc = (m0 - clip * a.L) / R;
+        const int clip = divL(m0), kc = (m0 - clip * L) / R;
         float *o = a.stats_out + ((size_t)(clip * a.nch + kc) * gpb + tid) * 2;
         o[0] = gmean[tid];
         o[1] = a2;
@@ -436,7 +442,13 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const ConvCbArgs a, const 
 // weight slice arrives as (hi, lo') fragment pairs, 48 x 1 KB contiguous per wave; three MFMAs per product into two accumulators.
 // One 128-channel block per workgroup (the two LDS images of a two-block panel would not fit the static 64 KB).
 template <int MT, bool PRO>
-__global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, const int mtiles, const unsigned bytes_src) {
+__global__ __launch_bounds__(256) void conv_cb_x3_kernel(const void *const src, const void *const wimg, const unsigned bytes_src, const int mtiles, const int M,
+                                                         const int L, const unsigned magicL, const int src_ld, const int N, const unsigned lg,
+                                                         const ConvCbArgs a) {
+  // argument head (12 dwords, preloaded into SGPRs with the wave: kernels.h, "argument heads"): what the prefetch test, the tile index, the
+  // panel loads and the weight-fragment loads need (lg = log2S | log2cpg << 8).  `a` arrives through scalar loads behind them; the head
+  // fields are NOT read from it here.
+  const int log2S = (int)(lg & 255u), log2cpg = (int)(lg >> 8);
   using frag = f16x8;
   constexpr int PITCHW = KC + 8, TPR = KC / 4, RPP = 256 / TPR;   // LDS pitch (fp16 elements), threads per panel row (16 B of fp32 each), rows per pass
   constexpr int BM = 32 * MT, PR = BM + 2, NV = (PR + RPP - 1) / RPP;
@@ -450,15 +462,15 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
     return;
   }
   const int mt = (int)blockIdx.y, ws = (int)blockIdx.x;
-  const int nt = ws >> a.log2S, cb = ws & ((1 << a.log2S) - 1);
-  const int r0 = mt * BM, M = a.B * a.L;
-  auto divL = [&](int x) { return (int)__umulhi((unsigned)x, a.magicL); };
+  const int nt = ws >> log2S, cb = ws & ((1 << log2S) - 1);
+  const int r0 = mt * BM;
+  auto divL = [&](int x) { return (int)__umulhi((unsigned)x, magicL); };
 
   // ---- 1. activation panel (fp32): rows r0 - 1 .. r0 + BM of channel block cb ----------------------------------------------------------
-  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.src), 0, bytes_src, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(src), 0, bytes_src, 0x00020000);
   const int cv = tid % TPR, pr = tid / TPR;
   f32x4 pv[NV];
-  const unsigned col_b = (unsigned)((cb * KC + cv * 4) * 4), row_b = (unsigned)(a.src_ld * 4);
+  const unsigned col_b = (unsigned)((cb * KC + cv * 4) * 4), row_b = (unsigned)(src_ld * 4);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int j = pr + RPP * i, r = r0 - 1 + j;
@@ -466,7 +478,7 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
     pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rS, ok ? (unsigned)r * row_b + col_b : OOB, 0, 0));
   }
   // ---- 2. GroupNorm operands (as in conv_cb_kernel; this thread owns a channel QUAD) ----------------------------------------------------
-  const int gshift = KC_LOG2 - a.log2cpg;
+  const int gshift = KC_LOG2 - log2cpg;
   const int clip0 = divL(max(r0 - 1, 0));
   const int nclip = PRO ? (divL(min(r0 + BM, M - 1)) - clip0 + 1) : 0;
   const int npair = nclip << gshift;
@@ -476,15 +488,15 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
   int lim = 0;
   const int sub = tid & 7;
   if constexpr (PRO) {
-    const int G = a.C >> a.log2cpg;
+    const int G = a.C >> log2cpg;
     ga = *reinterpret_cast<const f32x4 *>(a.gamma + cb * KC + cv * 4);
     be = *reinterpret_cast<const f32x4 *>(a.beta + cb * KC + cv * 4);
     const bool tiles = a.pro == 2;
-    const int ltpg = a.log2cpg - 5, ct = a.C >> 5;
+    const int ltpg = log2cpg - 5, ct = a.C >> 5;
     const int p = min(tid >> 3, npair - 1);
     const int slot = p >> gshift, gi = p & ((1 << gshift) - 1);
     const int clip = clip0 + slot;
-    const int mt_lo = (clip * a.L) >> 5, nmt = ((clip * a.L + a.L - 1) >> 5) - mt_lo + 1;
+    const int mt_lo = (clip * L) >> 5, nmt = ((clip * L + L - 1) >> 5) - mt_lo + 1;
     lim = tiles ? (nmt << max(ltpg, 0)) : a.nch;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -494,14 +506,14 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
       const unsigned off2 = (unsigned)(((mtile * ct + tile) * 2 + (clip - divL(mtile << 5))) * 2);
       const unsigned off1 = (unsigned)((((clip * a.nch + kc) * G) + (cb << gshift) + gi) * 2);
       cs[k] = *reinterpret_cast<const float2 *>(a.stats + (tiles ? off2 : off1));
-      cn[k] = part_count(tiles, clip, kc, mtile, a.L, a.chunk_rows, a.log2cpg);
+      cn[k] = part_count(tiles, clip, kc, mtile, L, a.chunk_rows, log2cpg);
     }
   }
   // ---- 3. the wave's weight slice: 24 (hi, lo') fragment pairs, 48 KB contiguous per wave, independent of the producer kernel -----------
   __builtin_amdgcn_sched_barrier(0);
   frag wh[24], wl[24];
   {
-    const frag *wp = reinterpret_cast<const frag *>(a.wp) + ((size_t)(cb * (a.N >> 5) + (nt * 4 + wave)) * 48) * 64;   // uniform
+    const frag *wp = reinterpret_cast<const frag *>(wimg) + ((size_t)(cb * (N >> 5) + (nt * 4 + wave)) * 48) * 64;   // uniform
 #pragma unroll
     for (int s = 0; s < 24; ++s) {
       wh[s] = wp[(2 * s) * 64 + lane];
@@ -515,7 +527,7 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
   }
   // ---- 4. statistics of the touched (clip, group) pairs -> LDS ---------------------------------------------------------------------------
   if constexpr (PRO) {
-    const float rn = 1.0f / ((float)a.L * (float)(1 << a.log2cpg));
+    const float rn = 1.0f / ((float)L * (float)(1 << log2cpg));
     const float2 st = merge_parts(cs, cn, sub, lim, rn, a.eps);
     const int p = tid >> 3;
     if (sub == 0 && p < npair) gstat[p >> gshift][p & ((1 << gshift) - 1)] = st;
@@ -529,7 +541,7 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
     if (j < PR) {
       f32x4 o = pv[i];
       if (PRO && r >= 0 && r < M) {
-        const float2 st = gstat[divL(r) - clip0][(cv * 4) >> a.log2cpg];
+        const float2 st = gstat[divL(r) - clip0][(cv * 4) >> log2cpg];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float sc = st.y * ga[e];
@@ -555,9 +567,9 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
   bool ok0[MT], ok2[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
-    const int m = r0 + t * 32 + fr, l = m - divL(m) * a.L;
+    const int m = r0 + t * 32 + fr, l = m - divL(m) * L;
     ok0[t] = l > 0;
-    ok2[t] = l < a.L - 1;
+    ok2[t] = l < L - 1;
   }
   f32x16 acc[MT], accL[MT];
 #pragma unroll
@@ -584,7 +596,7 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
         x3_mfma<X3_F16>(wh[tap * 8 + ks], wl[tap * 8 + ks], ah, al, acc[t], accL[t]);
       }
   // ---- 7. partial slab --------------------------------------------------------------------------------------------------------------------
-  float *sl = a.slab + (size_t)cb * M * a.N + nt * 128 + wave * 32 + 4 * fh;
+  float *sl = a.slab + (size_t)cb * M * N + nt * 128 + wave * 32 + 4 * fh;
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     const int m = r0 + t * 32 + fr;
@@ -594,7 +606,7 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const ConvCbArgs a, con
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaf(accL[t][4 * g + e], X3P<X3_F16>::INV, acc[t][4 * g + e]);
-        *reinterpret_cast<f32x4 *>(sl + (unsigned)(m * a.N + 8 * g)) = v;
+        *reinterpret_cast<f32x4 *>(sl + (unsigned)(m * N + 8 * g)) = v;
       }
     }
   }
@@ -854,6 +866,16 @@ hipError_t launch_pack_conv_cb(int dt, const float *w, int N, int C, void *out, 
   return hipGetLastError();
 }
 
+namespace {
+// The one launch site of the conv_cb kernels: the argument head (kernels.h, "argument heads") is built here, in the kernels' parameter order
+template <typename Kern> void launch_cb_head(Kern kern, const ConvCbArgs &a, dim3 grid, int mtiles, unsigned bytes_src, hipStream_t s) {
+  const void *const src = a.src, *const wimg = a.wp;
+  const int M = a.B * a.L, L = a.L, src_ld = a.src_ld, N = a.N;
+  const unsigned magicL = a.magicL, lg = (unsigned)a.log2S | ((unsigned)a.log2cpg << 8);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, src, wimg, bytes_src, mtiles, M, L, magicL, src_ld, N, lg, a);
+}
+}  // namespace
+
 hipError_t launch_conv_cb(int dt, const ConvCbArgs &a0, hipStream_t s) {
   if (!conv_cb_shape_ok(dt, a0.B, a0.L, a0.C, a0.N, a0.pro ? a0.G : 0)) return hipErrorInvalidValue;
   if (a0.pro == 1 && a0.nch > 32) return hipErrorInvalidValue;
@@ -890,19 +912,19 @@ hipError_t launch_conv_cb(int dt, const ConvCbArgs &a0, hipStream_t s) {
   const unsigned bytes_src = (unsigned)((size_t)M * a.src_ld * dsize(dt));
   if (dt == F32X) {
     if (a.pro) {
-      if (mt == 1) hipLaunchKernelGGL((conv_cb_x3_kernel<1, true>), grid, dim3(256), 0, s, a, mtiles, bytes_src);
-      else hipLaunchKernelGGL((conv_cb_x3_kernel<2, true>), grid, dim3(256), 0, s, a, mtiles, bytes_src);
+      if (mt == 1) launch_cb_head(conv_cb_x3_kernel<1, true>, a, grid, mtiles, bytes_src, s);
+      else launch_cb_head(conv_cb_x3_kernel<2, true>, a, grid, mtiles, bytes_src, s);
     } else {
-      if (mt == 1) hipLaunchKernelGGL((conv_cb_x3_kernel<1, false>), grid, dim3(256), 0, s, a, mtiles, bytes_src);
-      else hipLaunchKernelGGL((conv_cb_x3_kernel<2, false>), grid, dim3(256), 0, s, a, mtiles, bytes_src);
+      if (mt == 1) launch_cb_head(conv_cb_x3_kernel<1, false>, a, grid, mtiles, bytes_src, s);
+      else launch_cb_head(conv_cb_x3_kernel<2, false>, a, grid, mtiles, bytes_src, s);
     }
     return hipGetLastError();
   }
   if (a.epi) {
 #define SF_CBD(T, MT)                                                                                                          \
   do {                                                                                                                         \
-    if (a.epi == 1) hipLaunchKernelGGL((conv_cb_kernel<T, MT, false, 1, 1>), grid, dim3(256), 0, s, a, mtiles, bytes_src);     \
-    else hipLaunchKernelGGL((conv_cb_kernel<T, MT, true, 1, 2>), grid, dim3(256), 0, s, a, mtiles, bytes_src);                 \
+    if (a.epi == 1) launch_cb_head(conv_cb_kernel<T, MT, false, 1, 1>, a, grid, mtiles, bytes_src, s);     \
+    else launch_cb_head(conv_cb_kernel<T, MT, true, 1, 2>, a, grid, mtiles, bytes_src, s);                 \
   } while (0)
     if (dt == BF16) {
       if (mt == 1) SF_CBD(bf16, 1);
@@ -916,8 +938,8 @@ hipError_t launch_conv_cb(int dt, const ConvCbArgs &a0, hipStream_t s) {
   }
 #define SF_CB2(T, MT, KB_)                                                                                                \
   do {                                                                                                                    \
-    if (a.pro) hipLaunchKernelGGL((conv_cb_kernel<T, MT, true, KB_>), grid, dim3(256), 0, s, a, mtiles, bytes_src);       \
-    else hipLaunchKernelGGL((conv_cb_kernel<T, MT, false, KB_>), grid, dim3(256), 0, s, a, mtiles, bytes_src);            \
+    if (a.pro) launch_cb_head(conv_cb_kernel<T, MT, true, KB_>, a, grid, mtiles, bytes_src, s);       \
+    else launch_cb_head(conv_cb_kernel<T, MT, false, KB_>, a, grid, mtiles, bytes_src, s);            \
   } while (0)
 #define SF_CB(T, MT)                 \
   do {                               \

@@ -31,8 +31,17 @@ constexpr int LDR = 36;   // row pitch of a partial tile in LDS (floats)
 // in registers when it is multiplied (common.h, X3P<X3_F16>), three MFMAs per product, two accumulators.  16 registers per fragment in
 // flight: K <= 1280.
 template <typename T, bool CAT, int NFD, bool T1, bool X3 = false>
-__global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const ConvGemmArgs a, const int mtiles, const int ntiles, const int swz, const unsigned bytesA,
-                                                           const unsigned bytesA2, const unsigned bytesW) {
+__global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const void *const wimg, const void *const src, const unsigned bytesW, const unsigned bytesA,
+                                                           const int mtiles, const int ntiles_swz, const int K, const int M, const int Lout,
+                                                           const int Lsrc, const int src_ld, const unsigned geo, const ConvGemmArgs a,
+                                                           const unsigned bytesA2) {
+  // argument head (14 dwords, preloaded into SGPRs with the wave: kernels.h, "argument heads"): what the tile index, the weight-fragment
+  // loads and the first source's loads need.  `a` arrives through scalar loads behind them: in front of the epilogue-operand block nothing
+  // reads a head field from `a`; behind it the epilogue takes M, Lout, cin and the tile count from `a` again (the same values), so that the
+  // head's registers are free once the operand stream is out.
+  const int ntiles = ntiles_swz >> 1, swz = ntiles_swz & 1;
+  const int taps = (int)(geo & 255u), stride = (int)((geo >> 8) & 15u), pad = (int)((geo >> 12) & 255u), up_shift = (int)((geo >> 20) & 15u);
+  const int cin = (int)(geo >> 24) << 4;
   using frag = typename std::conditional<X3, f16x8, typename Frag16<T>::type>::type;
   constexpr int ES = X3 ? 4 : 2;
   static_assert(!X3 || sizeof(T) == 4, "split mode: fp32 activations");
@@ -43,28 +52,21 @@ __global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const ConvGemmArgs a,
     prefetch_slice(a.pf, (int)blockIdx.x - mtiles * ntiles, 256);
     return;
   }
-  int bid = blockIdx.x, mt, nt;
-  if (swz) {   // column tiles of one XCD share their weights' L2
-    const int xcd = bid & 7, j = bid >> 3;
-    nt = xcd + 8 * (j / mtiles);
-    mt = j % mtiles;
-  } else {
-    nt = bid / mtiles;
-    mt = bid % mtiles;
-  }
+  // swz: column tiles of one XCD share their weights' L2 (nt = xcd + 8 * (j / mtiles), j = bid / 8); else nt = bid / mtiles.  One division
+  // and no branch: the code up to the first loads is one block
+  const int bid = blockIdx.x, j = swz ? bid >> 3 : bid, jq = j / mtiles;
+  const int mt = j - jq * mtiles, nt = swz ? (bid & 7) + 8 * jq : jq;
   const int m0 = mt * 32, n0 = nt * 32;
   const int fr = lane & 31, fh = lane >> 5;
 
-  const bool has_res = a.res != nullptr, has_bs = a.bscale != nullptr, has_ba = a.badd != nullptr;
-  const bool ln_epi = a.ln_colsum != nullptr;
   const int ml = tid >> 3, nq = tid & 7;                 // epilogue: one thread = 4 consecutive columns of one row
   const int em = m0 + ml, enb = n0 + nq * 4;
 
   // ---- the wave's K quarter: all fragments in flight ----------------------------------------------------------------------------
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.src), 0, bytesA, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rA2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(CAT ? a.src2 : a.src), 0, CAT ? bytesA2 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rF = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(X3 ? a.wfrx : a.wfr), 0, bytesW, 0x00020000);
-  const int F = a.K >> 4, nf = F >> 2, f0 = wave * nf;          // K % 64 == 0: every wave takes F / 4 fragments of 16 k
+  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(src), 0, bytesA, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(CAT ? a.src2 : src), 0, CAT ? bytesA2 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rF = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(wimg), 0, bytesW, 0x00020000);
+  const int F = K >> 4, nf = F >> 2, f0 = wave * nf;          // K % 64 == 0: every wave takes F / 4 fragments of 16 k
   f32x16 acc, accL;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = accL[r] = 0.f;
@@ -72,25 +74,26 @@ __global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const ConvGemmArgs a,
   f32x4 eb, es_, ea, ec;
   u32x2 er, lp[4];
   u32x4 er4 = {0u, 0u, 0u, 0u};   // split mode: the residual quad in fp32
+  bool has_res, has_bs, has_ba, ln_epi;
   {
     const int m = m0 + fr;
-    const bool vm = m < a.M;
+    const bool vm = m < M;
     const int mm = vm ? m : 0;
-    const int b = mm / a.Lout, l = mm - b * a.Lout;
-    const int rb = b * a.Lsrc, p0 = l * a.stride - a.pad;
-    const int pmax = (a.Lsrc << a.up_shift) - 1;
+    const int b = mm / Lout, l = mm - b * Lout;
+    const int rb = b * Lsrc, p0 = l * stride - pad;
+    const int pmax = (Lsrc << up_shift) - 1;
     const unsigned vmask = vm ? 0u : OOB, lane_b = (unsigned)(fh * 8 * ES);
     const unsigned wbase = X3 ? (unsigned)((((size_t)nt * F + f0) * 128 + lane) * 16) : (unsigned)((((size_t)nt * F + f0) * 64 + lane) * 16);
     constexpr unsigned WSTEP = X3 ? 2048u : 1024u;   // bytes of one weight fragment (pair)
-    const int k_taps = a.taps * a.cin;
+    const int k_taps = taps * cin;
     // (tap, channel) of the wave's first fragment, then streamed: all of it wave-uniform (scalar registers)
     int k = f0 * 16;
-    int tap = (a.taps > 1 && k < k_taps) ? k / a.cin : 0;
-    int c = k - tap * a.cin;
+    int tap = (!T1 && taps > 1 && k < k_taps) ? k / cin : 0;   // (T1: one tap, no division in front of the loads)
+    int c = k - tap * cin;
     auto row_off = [&](int t) {
       const int p = p0 + t;
       const unsigned bad = ((unsigned)p > (unsigned)pmax) ? OOB : 0u;
-      return ((unsigned)(((rb + (max(p, 0) >> a.up_shift)) * a.src_ld) * ES) + lane_b) | bad | vmask;
+      return ((unsigned)(((rb + (max(p, 0) >> up_shift)) * src_ld) * ES) + lane_b) | bad | vmask;
     };
     unsigned cur = row_off(tap);
     const unsigned cur2 = CAT ? (((unsigned)(mm * a.src2_ld * ES) + lane_b) | vmask) : OOB;
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const ConvGemmArgs a,
         wf[i] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(rF, (wbase + (unsigned)(i * WSTEP)) | dead, 0, 0));
         k += 16;
         c += 16;
-        if (c >= a.cin && k < k_taps) {
+        if (c >= cin && k < k_taps) {
           c = 0;
           ++tap;
           cur = row_off(tap);
@@ -148,6 +151,12 @@ __global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const ConvGemmArgs a,
     // ---- epilogue operands: issued BEHIND the operand stream (they are needed last), branch-free -- an absent operand is a buffer
     //      resource of zero records, whose loads return zeros without touching memory (a `ptr ? load : 0` compiles to a branch with
     //      the load and an s_waitcnt vmcnt(0) inside it: five serial round trips in front of everything else)
+    //      Nothing of `a` is looked at in front of this point but the second source's fields: the scalar work on the epilogue's pointers
+    //      stays behind the barrier too (hoisted, it put a wait for the struct in front of the first load, and the one-tap concatenated forms
+    //      over the SGPR limit)
+    __builtin_amdgcn_sched_barrier(0);
+    has_res = a.res != nullptr, has_bs = a.bscale != nullptr, has_ba = a.badd != nullptr;
+    ln_epi = a.ln_colsum != nullptr;
     {
       auto rsrc = [](const void *p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, p ? 0x7FFFFFF0u : 0u, 0x00020000); };
       const int mc = min(em, a.M - 1), nc = min(enb, a.N - 4);
@@ -288,7 +297,9 @@ __global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const ConvGemmArgs a,
       const float dk = hi > lo ? t1 / (float)(hi - lo) : 0.f;
       t2 = fmaxf(fmaf(-32.f * t1, dk, t2), 0.f);
       t1 = p + dk;
-      *reinterpret_cast<float2 *>(a.gnpart_out + (((size_t)mt * ntiles + nt) * 2 + tid) * 2) = make_float2(t1, t2);
+      // (n_store + 31) >> 5 is the head's `ntiles` again, by launch_rs_head's formula (the head's registers are free by now): whoever
+      // changes the column tiling there changes it here
+      *reinterpret_cast<float2 *>(a.gnpart_out + (((size_t)mt * ((a.n_store + 31) >> 5) + nt) * 2 + tid) * 2) = make_float2(t1, t2);
     }
   }
 }
@@ -317,46 +328,53 @@ __global__ void pack_wfrx_kernel(const float *__restrict__ w, int N, int K, f16 
   }
 }
 
-template <bool CAT> hipError_t launch_rs_x3(const ConvGemmArgs &a, hipStream_t s) {
+// The one launch site: the argument head (kernels.h, "argument heads") is built here, in the kernel's parameter order.  wimg = the fragment-
+// ordered weight image the instantiation multiplies (wfr, or wfrx in split mode), es = bytes per activation element.
+// the head's packed geometry dword holds the launch: taps and cin / 16 in 8 bits each, pad in 8, stride and up_shift in 4.  conv_gemm_rs_ok
+// asks the same, so a launch outside these widths (a stride-16 patchify) is planned onto another kernel, not refused here
+bool rs_geo_fits(const ConvGemmArgs &a) {
+  return a.taps >= 1 && a.taps <= 255 && a.stride >= 0 && a.stride <= 15 && a.pad >= 0 && a.pad <= 255 && a.up_shift >= 0 && a.up_shift <= 15 &&
+         (a.cin % 16) == 0 && a.cin >= 0 && a.cin <= 255 * 16;
+}
+
+template <typename Kern> hipError_t launch_rs_head(Kern kern, const ConvGemmArgs &a, const void *wimg, size_t es, bool cat, hipStream_t s) {
+  if (!rs_geo_fits(a)) return hipErrorInvalidValue;
   const int mtiles = (a.M + 31) / 32, ntiles = (a.n_store + 31) / 32;
   const int swz = (ntiles % 8 == 0) ? 1 : 0;
-  const size_t bA = (size_t)(a.M / a.Lout + (a.M % a.Lout ? 1 : 0)) * a.Lsrc * a.src_ld * 4;
-  const size_t bA2 = CAT ? (size_t)a.M * a.src2_ld * 4 : 0;
-  const size_t bW = (size_t)a.N * a.K * 4;
+  const size_t bA = (size_t)(a.M / a.Lout + (a.M % a.Lout ? 1 : 0)) * a.Lsrc * a.src_ld * es;
+  const size_t bA2 = cat ? (size_t)a.M * a.src2_ld * es : 0;
+  const size_t bW = (size_t)a.N * a.K * es;
   const dim3 grid(mtiles * ntiles + (a.pf.ptr && a.pf.bytes >= 16 ? a.pf.wgs : 0));
+  const unsigned geo = (unsigned)a.taps | ((unsigned)a.stride << 8) | ((unsigned)a.pad << 12) | ((unsigned)a.up_shift << 20) | ((unsigned)(a.cin >> 4) << 24);
+  const void *const src = a.src;
+  const unsigned bytesW = (unsigned)bW, bytesA = (unsigned)bA, bytesA2 = (unsigned)bA2;
+  const int ntiles_swz = (ntiles << 1) | swz, K = a.K, M = a.M, Lout = a.Lout, Lsrc = a.Lsrc, src_ld = a.src_ld;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, wimg, src, bytesW, bytesA, mtiles, ntiles_swz, K, M, Lout, Lsrc, src_ld, geo, a, bytesA2);
+  return hipGetLastError();
+}
+
+template <bool CAT> hipError_t launch_rs_x3(const ConvGemmArgs &a, hipStream_t s) {
   const int nf = a.K / 64;
-#define SF_RSX(NFD)                                                                                                                                      \
-  do {                                                                                                                                                   \
-    if (a.taps == 1) hipLaunchKernelGGL((conv_gemm_rs_kernel<float, CAT, NFD, true, true>), grid, dim3(256), 0, s, a, mtiles, ntiles, swz, (unsigned)bA, (unsigned)bA2, (unsigned)bW); \
-    else hipLaunchKernelGGL((conv_gemm_rs_kernel<float, CAT, NFD, false, true>), grid, dim3(256), 0, s, a, mtiles, ntiles, swz, (unsigned)bA, (unsigned)bA2, (unsigned)bW); \
-  } while (0)
+#define SF_RSX(NFD) \
+  return a.taps == 1 ? launch_rs_head(conv_gemm_rs_kernel<float, CAT, NFD, true, true>, a, a.wfrx, 4, CAT, s) \
+                     : launch_rs_head(conv_gemm_rs_kernel<float, CAT, NFD, false, true>, a, a.wfrx, 4, CAT, s)
   if (nf <= 8) SF_RSX(8);
   else if (nf <= 12) SF_RSX(12);
   else if (nf <= 16) SF_RSX(16);
   else SF_RSX(20);
 #undef SF_RSX
-  return hipGetLastError();
 }
 
 template <typename T, bool CAT> hipError_t launch_rs(const ConvGemmArgs &a, hipStream_t s) {
-  const int mtiles = (a.M + 31) / 32, ntiles = (a.n_store + 31) / 32;
-  const int swz = (ntiles % 8 == 0) ? 1 : 0;
-  const size_t bA = (size_t)(a.M / a.Lout + (a.M % a.Lout ? 1 : 0)) * a.Lsrc * a.src_ld * 2;
-  const size_t bA2 = CAT ? (size_t)a.M * a.src2_ld * 2 : 0;
-  const size_t bW = (size_t)a.N * a.K * 2;
-  const dim3 grid(mtiles * ntiles + (a.pf.ptr && a.pf.bytes >= 16 ? a.pf.wgs : 0));
   const int nf = a.K / 64;
-#define SF_RS(NFD)                                                                                                                                       \
-  do {                                                                                                                                                   \
-    if (a.taps == 1) hipLaunchKernelGGL((conv_gemm_rs_kernel<T, CAT, NFD, true>), grid, dim3(256), 0, s, a, mtiles, ntiles, swz, (unsigned)bA, (unsigned)bA2, (unsigned)bW); \
-    else hipLaunchKernelGGL((conv_gemm_rs_kernel<T, CAT, NFD, false>), grid, dim3(256), 0, s, a, mtiles, ntiles, swz, (unsigned)bA, (unsigned)bA2, (unsigned)bW); \
-  } while (0)
+#define SF_RS(NFD) \
+  return a.taps == 1 ? launch_rs_head(conv_gemm_rs_kernel<T, CAT, NFD, true>, a, a.wfr, 2, CAT, s) \
+                     : launch_rs_head(conv_gemm_rs_kernel<T, CAT, NFD, false>, a, a.wfr, 2, CAT, s)
   if (nf <= 8) SF_RS(8);
   else if (nf <= 16) SF_RS(16);
   else if (nf <= 24) SF_RS(24);
   else SF_RS(32);
 #undef SF_RS
-  return hipGetLastError();
 }
 
 }  // namespace
@@ -368,6 +386,7 @@ bool conv_gemm_rs_ok(int dt, const ConvGemmArgs &a) {
   const bool x3 = dt == F32 && a.wfrx != nullptr && a.wx_mode == X3_F16;   // the split-operand form (fp32 activations)
   const size_t es = x3 ? 4 : 2;
   if (off || (dt == F32 && !x3) || (!x3 && !a.wfr) || a.geom != 0 || a.pro != 0 || a.taps < 1) return false;
+  if (!rs_geo_fits(a)) return false;   // the argument head's packed geometry (stride <= 15, pad <= 255, up_shift <= 15)
   if ((a.K % 64) || a.K > (x3 ? 1280 : 2048) || (a.cin % 16) || (a.cin2 % 16) || (a.N % 32) || a.n_store != a.N) return false;
   if (x3 && ((a.src_ld % 4) || (a.cin2 && (a.src2_ld % 4)) || a.out_f32)) return false;   // 16-byte fp32 fragment loads
   if ((a.res && (a.res_ld % 4)) || (a.bscale && (a.bscale_ld % 4)) || (a.badd && (a.badd_ld % 4)) || (a.out_ld % 4)) return false;   // vector epilogue loads

@@ -51,6 +51,21 @@ struct Prefetch {
   int wgs = 0;
 };
 
+// Argument heads.  The build preloads kernel arguments into SGPRs (Makefile, -amdgpu-kernarg-preload-count), but only LEADING scalar and
+// pointer parameters, 14 dwords at most (16 user SGPRs less the kernarg segment pointer), and nothing from the first by-value struct on.
+// A kernel that takes its argument block first therefore starts with scalar loads and a wait in front of its first address.  The
+// latency-bound kernels of the small-batch chain take a HEAD of up to 14 dwords in front of the block instead: what they need to test
+// for the hosted-prefetch workgroups, find their tile and issue their first global loads; small fields share a dword.  The block
+// itself is passed whole behind the head and arrives through scalar loads while those loads are in flight.
+//   conv_gemm_rs    weight image (wfr / wfrx), src, bytesW, bytesA, mtiles, ntiles << 1 | swz, K, M, Lout, Lsrc, src_ld,
+//                   geo = taps | stride << 8 | pad << 12 | up_shift << 20 | (cin / 16) << 24                                   (14 dwords)
+//                   (stride and up_shift in 4 bits, pad in 8: conv_gemm_rs_ok refuses what does not fit, the plan takes another kernel)
+//   conv_cb (+ x3)  src, wp, bytes_src, mtiles, M = B * L, L, magicL, src_ld, N, log2S | log2cpg << 8                          (12 dwords)
+// The block keeps every field (the host fills it as before and the launcher copies the head out of it), so a head field and its copy in
+// the block are equal by construction; up to its first loads a kernel reads the head only.  Each kernel has ONE launch site, which fills
+// the head in the kernel's parameter order (hipLaunchKernelGGL checks types, not the order of same-typed ints: tests/test_gpu_arg_head.py
+// runs the ragged shapes at which a swapped field shows).  tools/kernarg_preload_report.py shows what the compiler made of a signature
+// (profiles/kernarg_preload.txt).
 struct ConvGemmArgs {
   Prefetch pf;   // hosted prefetch (conv_gemm_wp / conv_gemm_fast only; other kernels ignore it)
   const void *src = nullptr, *src2 = nullptr, *w = nullptr, *res = nullptr;
