@@ -123,6 +123,20 @@ int sf_unet_forward(sf_unet *h, const float *x, const float *sigma, const float 
 int sf_vsample(sf_unet *h, float *x_inout, const float *const *ctx, const float *emb, int B, int L0,
                int num_steps, float embedding_scale, int use_graph, void *ws, int64_t ws_bytes, void *stream);
 
+/* The inpainting loop  x <- VInpainter(net)(source, mask, num_steps, num_resamples, x_noisy = x, ...)  in place  (SURVEY.md A.6):
+ *   sf_vsample's loop over num_steps * num_resamples iterations; after each v-step, where mask != 0, x is replaced by the source re-noised
+ *   to the iteration's target level,  alpha * source + beta * z,  z = the standard normals of sf_op_philox_normal(seed, iteration, element).
+ *   A resample (all but the last iteration of a step) re-noises to the step's OWN level.  The last iteration has beta == 0: where the mask
+ *   is set the result is the source, bit for bit.
+ *   x_inout, source: (B, in_channels, L0) fp32.  mask: (B, in_channels, L0), one byte per element, non-zero = keep the source.
+ *   Neither source nor mask is written.  Conditioning, graph use and the single host synchronisation are sf_vsample's; the step graph is
+ *   cached separately from sf_vsample's and replayed for any later source / mask / seed of the same shape, workspace and guidance scale.
+ *   The workspace is larger than sf_vsample's (source, mask and seed live in it): sf_vinpaint_workspace_bytes. */
+int64_t sf_vinpaint_workspace_bytes(const sf_unet *h, int B, int L0, int two_pass, int num_steps, int num_resamples);
+int sf_vinpaint(sf_unet *h, float *x_inout, const float *source, const uint8_t *mask, const float *const *ctx, const float *emb, int B,
+                int L0, int num_steps, int num_resamples, uint64_t seed, float embedding_scale, int use_graph, void *ws, int64_t ws_bytes,
+                void *stream);
+
 /* Debug taps (tests only): after the next sf_unet_forward, every block-level activation is
  * copied as fp32 channels-last rows into `buf` (device).  Query the table afterwards. */
 int sf_unet_debug_enable(sf_unet *h, float *buf, int64_t cap_floats);
@@ -277,6 +291,18 @@ int sf_times_to_track(const double *times, const int32_t *clip_of, int n_times, 
  * Op-level entry points (channels-last, used by tests/ to localise kernel bugs).
  *   dtype selects the storage type of x / w / out (fp32 or bf16 bit patterns).
  * ---------------------------------------------------------------------------------------- */
+/* Counter-based device noise (the inpainting loop's randn_like): out[i], i in [0, n), is the standard normal of element e = elem_offset + i
+ * at iteration k -- a pure function of (seed, k, e).  r[0..3] = Philox4x32-10(counter = (g lo, g hi, k, 0), key = (seed lo, seed hi)) with
+ * g = e >> 2;  u(w) = ((w >> 9) + 0.5) * 2^-23;  (z0, z1) = sqrt(-2 ln u(r0)) * (cos, sin)(2 pi u(r1)), (z2, z3) likewise from r2, r3;
+ * element e takes z[e & 3].  out: device, fp32. */
+int sf_op_philox_normal(uint64_t seed, uint32_t k, int64_t elem_offset, int64_t n, float *out, void *stream);
+/* One launch of the inpainting loop's update on the elements [e0, e1) of whole (B, C, L) tensors (every pointer is the base of the WHOLE tensor;
+ * device memory): with k = *step_idx and (a0, b0, a1, b1) = sched[4k .. 4k+3],
+ *   x[e] <- mask[e] ? a1 * source[e] + b1 * z(seed, k, e) : a1 * (a0 x - b0 v) + b1 * (b0 x + a0 v),   v = v_uncond ? v_u + (v - v_u) * scale : v
+ * (z as sf_op_philox_normal; seed: two 32-bit words lo, hi).  The result of an element does not depend on how [0, n) is cut into ranges, nor on
+ * the alignment of the pointers (16-byte accesses only where every base allows them). */
+int sf_op_vinpaint_update(float *x, const float *v, const float *v_uncond, float scale, const float *source, const uint8_t *mask,
+                          const float *sched, const int32_t *step_idx, const uint32_t *seed, int64_t e0, int64_t e1, void *stream);
 /* out = conv1d(silu(groupnorm(x))) + bias (+ residual).  x:(B,L,C) and out/residual:(B,Lout,N) channels-last in
  * `dtype`; w:(N,C,taps) fp32 in PyTorch layout (packed internally); groups==0 -> no norm/activation;
  * upsample = nearest-neighbour factor applied before the convolution.  Lout = (L*upsample + 2*pad - taps)/stride + 1. */

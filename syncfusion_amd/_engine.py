@@ -209,6 +209,45 @@ class UNetEngine(_Base):
                                       _lib.stream_ptr(self.device)), "sf_vsample")
         return x
 
+    def inpaint(self, source: torch.Tensor, mask: torch.Tensor, num_steps: int, num_resamples: int, channels: Sequence[torch.Tensor],
+                embedding: torch.Tensor, embedding_scale: float = 1.0, x_noisy: Optional[torch.Tensor] = None, seed: int = 0,
+                use_graph: bool = True) -> torch.Tensor:
+        """``VInpainter``'s loop inside ``sf_vinpaint``.  ``mask`` (bool, the source's shape or broadcastable to it): True keeps the
+        source.  ``source``, ``mask`` and ``x_noisy`` are left untouched."""
+        _lib.require_gpu_tensor(source, "DiffusionModel.inpaint")
+        self._check_inputs(source, channels, embedding)
+        if int(num_steps) < 1 or int(num_resamples) < 1:
+            raise ValueError(f"num_steps and num_resamples must be >= 1, got {num_steps} and {num_resamples}")
+        if mask.dtype != torch.bool:
+            raise TypeError(f"mask must be a bool tensor, got {mask.dtype}")
+        try:
+            mask_b = torch.broadcast_to(mask.to(self.device), source.shape)
+        except RuntimeError as e:
+            raise ValueError(f"mask of shape {tuple(mask.shape)} does not broadcast to the source's {tuple(source.shape)}") from e
+        B, _, L0 = source.shape
+        with torch.cuda.device(self.device):
+            src = _lib.f32c(source)
+            mk = mask_b.contiguous()
+            if x_noisy is None:
+                x = torch.randn(src.shape, dtype=torch.float32, device=self.device)
+            else:
+                if tuple(x_noisy.shape) != tuple(source.shape):
+                    raise ValueError(f"x_noisy must have the source's shape {tuple(source.shape)}, got {tuple(x_noisy.shape)}")
+                _lib.require_gpu_tensor(x_noisy, "DiffusionModel.inpaint")
+                x = _lib.f32c(x_noisy).clone()
+            ctx = [_lib.f32c(c) for c in channels]
+            emb = _lib.f32c(embedding)
+            two = float(embedding_scale) != 1.0
+            # sized for at least 256 iterations, as sample()'s: a later call with more finds the same buffer and the cached step graph
+            n = self.lib.sf_vinpaint_workspace_bytes(self.handle, B, L0, int(two), max(int(num_steps) * int(num_resamples), 256), 1)
+            if n < 0:
+                raise _lib.SyncFusionAmdError(f"unsupported shape B={B}, L0={L0}: {self.lib.sf_last_error().decode()}")
+            ws = self._workspace(n, self.device)
+            check(self.lib.sf_vinpaint(self.handle, x.data_ptr(), src.data_ptr(), mk.data_ptr(), _lib.ptr_array(ctx), emb.data_ptr(), B, L0,
+                                       int(num_steps), int(num_resamples), int(seed) & 0xFFFFFFFFFFFFFFFF, float(embedding_scale),
+                                       int(bool(use_graph)), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device)), "sf_vinpaint")
+        return x
+
     def launch_count(self) -> int:
         return int(self.lib.sf_unet_launch_count(self.handle))
 

@@ -86,6 +86,10 @@ SYMBOLS = {
     "sf_vsample_workspace_bytes": (_L, [_P, _I, _I, _I, _I]),
     "sf_unet_forward": (_I, [_P, _P, _P, C.POINTER(_P), _P, _I, _I, _F, _P, _P, _L, _P]),
     "sf_vsample": (_I, [_P, _P, C.POINTER(_P), _P, _I, _I, _I, _F, _I, _P, _L, _P]),
+    "sf_vinpaint_workspace_bytes": (_L, [_P, _I, _I, _I, _I, _I]),
+    "sf_vinpaint": (_I, [_P, _P, _P, _P, C.POINTER(_P), _P, _I, _I, _I, _I, C.c_uint64, _F, _I, _P, _L, _P]),
+    "sf_op_philox_normal": (_I, [C.c_uint64, C.c_uint32, _L, _L, _P, _P]),
+    "sf_op_vinpaint_update": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _L, _L, _P]),
     "sf_unet_debug_enable": (_I, [_P, _P, _L]),
     "sf_unet_debug_count": (_I, [_P]),
     "sf_unet_debug_info": (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_L), C.POINTER(_L), C.POINTER(C.c_int32)]),

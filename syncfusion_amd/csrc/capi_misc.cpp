@@ -136,6 +136,23 @@ int sf_times_to_track(const double *times, const int32_t *clip_of, int n_times, 
   SF_API_END
 }
 
+int sf_op_philox_normal(uint64_t seed, uint32_t k, int64_t elem_offset, int64_t n, float *out, void *stream) {
+  SF_API_BEGIN
+  if (!out || n < 1 || elem_offset < 0 || elem_offset > INT64_MAX - n) fail(SF_ERR_INVALID, "bad argument");
+  SF_HIP(launch_philox_normal(seed, k, elem_offset, n, out, static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_vinpaint_update(float *x, const float *v, const float *v_uncond, float scale, const float *source, const uint8_t *mask, const float *sched,
+                          const int32_t *step_idx, const uint32_t *seed, int64_t e0, int64_t e1, void *stream) {
+  SF_API_BEGIN
+  if (!x || !v || !source || !mask || !sched || !step_idx || !seed || e0 < 0 || e1 < e0) fail(SF_ERR_INVALID, "bad argument");
+  SF_HIP(launch_vinpaint_update(x, v, v_uncond, scale, source, mask, sched, step_idx, 0, seed, e0, e1, static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
 int sf_cut_prefix_crop(const float *gen, const float *y, int B, int C, int L, int cut_length, float *out, int32_t *first_onset, void *stream) {
   SF_API_BEGIN
   if (!gen || !y || !out || !first_onset || B < 1 || C < 1 || L < 1 || cut_length < 1 || cut_length > L) fail(SF_ERR_INVALID, "bad argument");

@@ -367,6 +367,16 @@ hipError_t launch_time_fourier(int dt, const float *sig, const int *sig_idx, con
 //   x <- a1*(a0*x - b0*v) + b1*(b0*x + a0*v),  (a0,b0,a1,b1) = sched[*step_idx][0..3].
 hipError_t launch_vsampler_update(float *x, const float *v, const float *v_uncond, float scale, const float *sched,
                                   const int *step_idx, int64_t n, hipStream_t s);
+// VInpainter iteration (sampler.hip), in place on x, for the elements [e0, e1) of the whole tensor (all pointers are bases of the WHOLE
+// (B, C, L) tensor; a clip-parallel branch passes its slice as the range):
+//   x <- mask ? a1*source + b1*z : (the v-sampler step above),  z = philox normal(seed[0..1], k, element),  k = *step_idx + step_bias,
+//   (a0,b0,a1,b1) = sched[k][0..3].  seed: two 32-bit words (lo, hi) in device memory.
+hipError_t launch_vinpaint_update(float *x, const float *v, const float *v_uncond, float scale, const float *source, const uint8_t *mask,
+                                  const float *sched, const int *step_idx, int step_bias, const uint32_t *seed, int64_t e0, int64_t e1,
+                                  hipStream_t s);
+// out[i] = standard normal of element (elem_offset + i) at virtual iteration k: Philox4x32-10 with counter (g lo, g hi, k, 0), g = element >> 2,
+// key (seed lo, seed hi), Box-Muller on u(w) = ((w >> 9) + 0.5) * 2^-23; lane = element & 3 ("Inpainting sampler")
+hipError_t launch_philox_normal(uint64_t seed, uint32_t k, int64_t elem_offset, int64_t n, float *out, hipStream_t s);
 // cur[0..ld) = table[*step_idx][0..ld), then (*step_idx)++  (single workgroup; first kernel of a sampling step)
 hipError_t launch_step_select(const float *table, int ld, int *step_idx, float *cur, hipStream_t s);
 // one wave busy-waits for `microseconds` (tuning aid)

@@ -81,6 +81,10 @@ struct Plan {  // everything carved out of the caller's workspace for one (B, L0
   int mod_stride = 0;
   float *mod_steps = nullptr;
   int steps_cap = 0;
+  // inpainting loop only (sf_vinpaint): the kept source, its mask (one byte per element) and the noise seed (lo, hi) the update kernel reads
+  float *src = nullptr;
+  uint8_t *mask = nullptr;
+  uint32_t *seed = nullptr;
 };
 
 }  // namespace
@@ -124,7 +128,7 @@ struct sf_unet {
     return ev_pool[ev_used++];
   }
   std::vector<std::pair<std::string, int64_t>> names;
-  // graph cache for sf_vsample
+  // graph cache for sf_vsample / sf_vinpaint
   bool no_ln_fusion = tune_env("SF_NO_LN_FUSION") != nullptr;   // debugging aid: launch every LayerNorm separately
   bool no_indep_branches = tune_env("SF_NO_INDEP_BRANCHES") != nullptr;   // debugging aid: fork / join the branches inside every step
   bool no_thin_tail = tune_env("SF_NO_THIN_TAIL") != nullptr;   // debugging aid: conv2 / inject of the thin levels as two launches
@@ -137,10 +141,11 @@ struct sf_unet {
   struct GraphKey {
     int B = 0, L0 = 0, T = 0, nbr = 0;
     bool two = false, valid = false;
+    bool inpaint = false;   // sf_vinpaint's step (other update kernel, other workspace layout) never replays sf_vsample's, nor the reverse
     float scale = 0.f;
     const void *ws = nullptr;
     bool operator==(const GraphKey &o) const {
-      return valid && o.valid && B == o.B && L0 == o.L0 && T == o.T && nbr == o.nbr && two == o.two && scale == o.scale && ws == o.ws;
+      return valid && o.valid && inpaint == o.inpaint && B == o.B && L0 == o.L0 && T == o.T && nbr == o.nbr && two == o.two && scale == o.scale && ws == o.ws;
     }
   } gkey;
   // Step graphs of OTHER recently used (shape, workspace, guidance) combinations: a server alternating between a few request
@@ -604,8 +609,9 @@ void build(sf_unet &u, const WeightMap *wm, hipStream_t s) {
 // workspace plan
 // ---------------------------------------------------------------------------------------------------
 constexpr int kSchedSteps = 1024;   // schedule capacity that keeps the workspace layout independent of num_steps
+constexpr int64_t kMaxVirtualSteps = 1 << 24;   // sf_vinpaint: num_steps * num_resamples (an int row count everywhere below)
 
-Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num_steps) {
+Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num_steps, bool inpaint = false) {
   const sf_unet_config &c = u.cfg;
   Plan p;
   p.B = B;
@@ -742,6 +748,14 @@ Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num
   p.emb_t = ws.alloc((int64_t)p.Bt * c.embedding_features * es);
   p.xhat_e = ws.alloc((int64_t)p.Bt * c.embedding_features * es);
   p.v_all = ws.alloc((int64_t)p.Bt * (u.n_ca > 0 ? u.n_ca : 1) * u.hd * es);
+  // The inpainting loop's own buffers: only in ITS layout (sf_vsample's is what it was), and in front of everything whose size depends on the
+  // number of steps, so that their addresses do not (the cached step graph holds them).
+  if (inpaint) {
+    const int64_t n = (int64_t)B * L0 * c.in_channels;
+    p.src = ws.alloc_n<float>(n);
+    p.mask = ws.alloc_n<uint8_t>(n);
+    p.seed = ws.alloc_n<uint32_t>(4);
+  }
   // Everything whose SIZE depends on the number of steps comes last, so that no other address does: a step graph
   // instantiated for one num_steps stays valid for another (up to kSchedSteps; the tables are indexed by the device
   // step counter).  Order: step counter, schedule (fixed capacity), sigmas, modulation table, time-MLP rows.
@@ -1689,10 +1703,10 @@ struct Exec {
   }
 };
 
-void check_ws(const sf_unet *h, void *ws, int64_t ws_bytes, int B, int L0, bool two, int steps) {
+void check_ws(const sf_unet *h, void *ws, int64_t ws_bytes, int B, int L0, bool two, int steps, bool inpaint = false) {
   if (!ws) fail(SF_ERR_WORKSPACE, "workspace is null");
   Workspace dry(nullptr, 0);
-  make_plan(*h, dry, B, L0, two, steps);
+  make_plan(*h, dry, B, L0, two, steps, inpaint);
   if (dry.used() > ws_bytes) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes, have %lld", (long long)dry.used(), (long long)ws_bytes);
 }
 
@@ -1818,19 +1832,28 @@ int sf_unet_forward(sf_unet *h, const float *x, const float *sigma, const float 
   SF_API_END
 }
 
-int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, int B, int L0, int num_steps, float embedding_scale,
-               int use_graph, void *ws, int64_t ws_bytes, void *stream) {
-  SF_API_BEGIN
-  if (!h || !x || !ctx) fail(SF_ERR_INVALID, "null argument");
-  if (!emb) fail(SF_ERR_INVALID, "ClassifierFreeGuidancePlugin requires embedding");
-  if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
+// The sampling loop behind sf_vsample and sf_vinpaint.  `inp` == nullptr: VSampler, num_steps steps.  Otherwise VInpainter: the same loop over
+// num_steps * num_resamples virtual steps -- virtual step k = i * R + r has the schedule row (alpha_i, beta_i, alpha_{i+j}, beta_{i+j}),
+// j = (r == R - 1), and sigma_i -- whose update launch also blends the re-noised source in where the mask is set.
+struct InpaintArgs {
+  const float *source;
+  const uint8_t *mask;
+  int num_resamples;
+  uint64_t seed;
+};
+
+static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const float *const *ctx, const float *emb, int B, int L0, int num_steps,
+                        float embedding_scale, int use_graph, void *ws, int64_t ws_bytes, void *stream) {
+  const char *const tag = inp ? "sf_vinpaint" : "sf_vsample";
+  const int R = inp ? inp->num_resamples : 1;
+  const int T = num_steps * R;   // (virtual) steps of the loop
   const bool two = embedding_scale != 1.0f;
-  check_ws(h, ws, ws_bytes, B, L0, two, num_steps);
+  check_ws(h, ws, ws_bytes, B, L0, two, T, inp != nullptr);
   Workspace w(ws, ws_bytes);
-  Plan p = make_plan(*h, w, B, L0, two, num_steps);
+  Plan p = make_plan(*h, w, B, L0, two, T, inp != nullptr);
   hipStream_t user = static_cast<hipStream_t>(stream);
   hipStream_t s = user;
-  if (use_graph && num_steps > 1) {
+  if (use_graph && T > 1) {
     if (!h->own_stream) {
       SF_HIP(sf_unet::make_branch_stream(&h->own_stream, 0, p.nbr));
       SF_HIP(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
@@ -1870,26 +1893,27 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
   ex.conditioning(ctx, emb);
   if (timing) {
     SF_HIP(hipStreamSynchronize(s));
-    fprintf(stderr, "[sf_vsample] conditioning %.3f ms\n", ms_since(t_begin));
+    fprintf(stderr, "[%s] conditioning %.3f ms\n", tag, ms_since(t_begin));
   }
 
   // LinearSchedule(1 -> 0) and (alpha, beta) = (cos, sin)(sigma*pi/2), exactly as VSampler builds them in fp32
   // (torch.linspace: start + i*step for the first half, end - (steps-1-i)*step for the second).
-  const int T = num_steps;
-  std::vector<float> sig(T + 1), host(4 * (size_t)T + (size_t)T);
+  const int S = num_steps;
+  std::vector<float> sig(S + 1), host(4 * (size_t)T + (size_t)T);
   {
-    const float step = (0.0f - 1.0f) / (float)T;
-    const int halfway = (T + 1) / 2;
-    for (int i = 0; i <= T; ++i) sig[i] = (i < halfway) ? (1.0f + step * (float)i) : (0.0f - step * (float)(T - i));
+    const float step = (0.0f - 1.0f) / (float)S;
+    const int halfway = (S + 1) / 2;
+    for (int i = 0; i <= S; ++i) sig[i] = (i < halfway) ? (1.0f + step * (float)i) : (0.0f - step * (float)(S - i));
   }
   const float hp = (float)(M_PI / 2.0);
-  for (int i = 0; i < T; ++i) {
-    float a0 = cosf(sig[i] * hp), b0 = sinf(sig[i] * hp), a1 = cosf(sig[i + 1] * hp), b1 = sinf(sig[i + 1] * hp);
-    host[4 * i + 0] = a0;
-    host[4 * i + 1] = b0;
-    host[4 * i + 2] = a1;
-    host[4 * i + 3] = b1;
-    host[4 * (size_t)T + i] = sig[i];
+  for (int k = 0; k < T; ++k) {
+    const int i = k / R, i1 = i + ((k % R) == R - 1 ? 1 : 0);   // a resample re-noises to the SAME level; the last one of a step moves on
+    float a0 = cosf(sig[i] * hp), b0 = sinf(sig[i] * hp), a1 = cosf(sig[i1] * hp), b1 = sinf(sig[i1] * hp);
+    host[4 * (size_t)k + 0] = a0;
+    host[4 * (size_t)k + 1] = b0;
+    host[4 * (size_t)k + 2] = a1;
+    host[4 * (size_t)k + 3] = b1;
+    host[4 * (size_t)T + k] = sig[i];
   }
   float *sched = p.sched;
   float *sigs = p.sigs;
@@ -1898,6 +1922,14 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
   SF_HIP(hipMemsetAsync(p.step, 0, 16 * sizeof(int), s));
 
   const int64_t n = (int64_t)B * L0 * h->cfg.in_channels;
+  // What differs from call to call reaches the (possibly replayed) update launch through the workspace, as x does through p.xs: the caller's
+  // source and mask are copied in, the seed sits in a slot of its own.  (seed_words outlives the copy: the synchronisation below.)
+  const uint32_t seed_words[2] = {inp ? (uint32_t)(inp->seed & 0xffffffffu) : 0u, inp ? (uint32_t)(inp->seed >> 32) : 0u};
+  if (inp) {
+    SF_HIP(hipMemcpyAsync(p.src, inp->source, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SF_HIP(hipMemcpyAsync(p.mask, inp->mask, n, hipMemcpyDeviceToDevice, s));
+    SF_HIP(hipMemcpyAsync(p.seed, seed_words, sizeof(seed_words), hipMemcpyHostToDevice, s));
+  }
   // sigma_i is the same for every clip, so the time MLP and the 42 Modulation / SkipModulate projections of ALL steps
   // are one set of GEMMs with M = num_steps, once per call (instead of five launches inside every step); a step then
   // starts by selecting its row (which also advances the device step counter) and every consumer reads that one row
@@ -1909,14 +1941,22 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
   }
   float *xs = p.xs;
   SF_HIP(hipMemcpyAsync(xs, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // the update launch of the elements [e0, e1) on stream `su`; `ahead`: the step counter has already been advanced (*counter == i + 1)
+  auto update = [&](int64_t e0, int64_t e1, const int *counter, bool ahead, hipStream_t su) {
+    const float *vu = two ? p.vout + n : nullptr;
+    if (inp)
+      SF_HIP(launch_vinpaint_update(xs, p.vout, vu, embedding_scale, p.src, p.mask, sched, counter, ahead ? -1 : 0, p.seed, e0, e1, su));
+    else
+      SF_HIP(launch_vsampler_update(xs + e0, p.vout + e0, vu ? vu + e0 : nullptr, embedding_scale, ahead ? sched - 4 : sched, counter, e1 - e0, su));
+  };
   auto one_step = [&]() {
     if (pre) {
       SF_HIP(launch_step_select(p.mod_steps, h->mod_ld, p.step, p.mod_all, s));
       ex.eval(xs, nullptr, nullptr, /*features_ready=*/true);
-      SF_HIP(launch_vsampler_update(xs, p.vout, two ? p.vout + n : nullptr, embedding_scale, sched - 4, p.step, n, s));   // *step == i + 1 here
+      update(0, n, p.step, true, s);
     } else {
       ex.eval(xs, sigs, p.step);
-      SF_HIP(launch_vsampler_update(xs, p.vout, two ? p.vout + n : nullptr, embedding_scale, sched, p.step, n, s));
+      update(0, n, p.step, false, s);
       SF_HIP(launch_step_advance(p.step, s));
     }
   };
@@ -1927,6 +1967,7 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
   key.T = T > kSchedSteps ? T : 0;   // the layout (hence the graph) depends on num_steps only beyond the fixed schedule capacity
   key.nbr = p.nbr;
   key.two = two;
+  key.inpaint = inp != nullptr;
   key.scale = embedding_scale;
   key.ws = ws;
   key.valid = true;
@@ -1935,7 +1976,7 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
   // before `host` dies, and the step graphs are measurably faster when their streams are idle at the first launch
   // (449 vs 408 steps/s at 50 steps: launching onto busy streams leaves the two branch pipelines out of phase).
   SF_HIP(hipStreamSynchronize(s));
-  if (timing) fprintf(stderr, "[sf_vsample] + schedule, per-step features: %.3f ms since entry\n", ms_since(t_begin));
+  if (timing) fprintf(stderr, "[%s] + schedule, per-step features: %.3f ms since entry\n", tag, ms_since(t_begin));
   // Independent branch pipelines.  Without guidance the clip slices never interact during the whole loop, so each
   // branch owns a step counter, a modulation row and a SINGLE-STREAM step graph replayed on its own stream; the streams
   // meet only at the end of the call.  (A two-stream graph with a fork/join per step costs ~1.7 ms of host time per launch
@@ -1953,7 +1994,7 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
       Exec eb{*h, v, sb};
       float *xb = xs + (v.x2 - p.x2);
       eb.block(0, xb, F32, v.vout, F32);
-      SF_HIP(launch_vsampler_update(xb, v.vout, nullptr, embedding_scale, sched - 4, p.step + br, nb, sb));
+      update(v.vout - p.vout, (v.vout - p.vout) + nb, p.step + br, true, sb);   // the branch's slice, by its GLOBAL element range
     };
     SF_HIP(hipEventRecord(h->ev_fork, s));
     for (int br = 1; br < p.nbr; ++br) SF_HIP(hipStreamWaitEvent(h->bstream[br], h->ev_fork, 0));
@@ -2008,14 +2049,14 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
     // caller that goes on to hipDeviceSynchronize (torch.cuda.synchronize) slows the GPU side by ~10 % (404-418 vs 448
     // steps/s); waiting on the one stream that joins the branches does not.
     SF_HIP(hipStreamSynchronize(s));
-    if (timing) fprintf(stderr, "[sf_vsample] %d steps x %d independent branch graphs: enqueue %.3f ms, done after %.3f ms\n", T, p.nbr, enq, ms_since(t_l));
+    if (timing) fprintf(stderr, "[%s] %d steps x %d independent branch graphs: enqueue %.3f ms, done after %.3f ms\n", tag, T, p.nbr, enq, ms_since(t_l));
   } else if (use_graph && T > 1 && h->gexec && !h->gexec_indep && !h->prof_on && h->gkey == key) {
     const auto t_l = now();
     for (int i = 0; i < T; ++i) SF_HIP(hipGraphLaunch(h->gexec, s));   // steady state: no eager step, no capture
     if (timing) {
       const double enq = ms_since(t_l);
       SF_HIP(hipStreamSynchronize(s));
-      fprintf(stderr, "[sf_vsample] %d graph launches: enqueue %.3f ms, done after %.3f ms\n", T, enq, ms_since(t_l));
+      fprintf(stderr, "[%s] %d graph launches: enqueue %.3f ms, done after %.3f ms\n", tag, T, enq, ms_since(t_l));
     }
   } else {
   h->launches = 0;
@@ -2057,6 +2098,42 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
     SF_HIP(hipStreamWaitEvent(user, h->ev_out, 0));
   }
   fail_guard.armed = false;
+}
+
+int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, int B, int L0, int num_steps, float embedding_scale,
+               int use_graph, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!h || !x || !ctx) fail(SF_ERR_INVALID, "null argument");
+  if (!emb) fail(SF_ERR_INVALID, "ClassifierFreeGuidancePlugin requires embedding");
+  if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
+  run_sampler(h, x, nullptr, ctx, emb, B, L0, num_steps, embedding_scale, use_graph, ws, ws_bytes, stream);
+  return SF_OK;
+  SF_API_END
+}
+
+int64_t sf_vinpaint_workspace_bytes(const sf_unet *h, int B, int L0, int two_pass, int num_steps, int num_resamples) {
+  try {
+    if (!h) fail(SF_ERR_INVALID, "null handle");
+    if (num_steps < 1 || num_resamples < 1) fail(SF_ERR_INVALID, "num_steps and num_resamples must be >= 1");
+    if ((int64_t)num_steps * num_resamples > kMaxVirtualSteps) fail(SF_ERR_INVALID, "num_steps * num_resamples is too large");
+    Workspace dry(nullptr, 0);
+    make_plan(*h, dry, B, L0, two_pass != 0, num_steps * num_resamples, true);
+    return dry.used();
+  } catch (const EngineError &) {
+    return -1;
+  }
+}
+
+int sf_vinpaint(sf_unet *h, float *x, const float *source, const uint8_t *mask, const float *const *ctx, const float *emb, int B, int L0,
+                int num_steps, int num_resamples, uint64_t seed, float embedding_scale, int use_graph, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!h || !x || !source || !mask || !ctx) fail(SF_ERR_INVALID, "null argument");
+  if (!emb) fail(SF_ERR_INVALID, "ClassifierFreeGuidancePlugin requires embedding");
+  if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
+  if (num_resamples < 1) fail(SF_ERR_INVALID, "num_resamples must be >= 1");
+  if ((int64_t)num_steps * num_resamples > kMaxVirtualSteps) fail(SF_ERR_INVALID, "num_steps * num_resamples is too large");
+  const InpaintArgs inp{source, mask, num_resamples, seed};
+  run_sampler(h, x, &inp, ctx, emb, B, L0, num_steps, embedding_scale, use_graph, ws, ws_bytes, stream);
   return SF_OK;
   SF_API_END
 }

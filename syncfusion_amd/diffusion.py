@@ -300,6 +300,57 @@ class VSampler(nn.Module):
         return self._net.engine().sample(x_noisy, num_steps, channels, embedding, embedding_scale, self.use_graph)
 
 
+def philox_normal(shape, seed: int, k: int, device, elem_offset: int = 0) -> Tensor:
+    """The standard normals the inpainting loop draws at virtual iteration ``k`` for a contiguous tensor of ``shape`` (fp32, on
+    ``device``): a pure function of (``seed``, ``k``, flat element index) -- Philox4x32-10 and Box-Muller, DESIGN.md "Inpainting
+    sampler".  ``elem_offset``: the flat index of the first element (a draw at an offset is the matching slice of a larger draw)."""
+    device = torch.device(device)
+    out = torch.empty(tuple(shape) if not isinstance(shape, int) else (shape,), dtype=torch.float32, device=device)
+    _lib.require_gpu_tensor(out, "philox_normal")
+    if not 0 <= int(k) < 2 ** 32:
+        raise ValueError(f"k must be in [0, 2**32), got {k}")
+    if int(elem_offset) < 0:
+        raise ValueError(f"elem_offset must be >= 0, got {elem_offset}")
+    if out.numel():
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().sf_op_philox_normal(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k), int(elem_offset), out.numel(),
+                                                       out.data_ptr(), _lib.stream_ptr(device)), "sf_op_philox_normal")
+    return out
+
+
+class VInpainter(nn.Module):
+    """``audio_diffusion_pytorch.VInpainter`` [RECALLED, UNPINNED: SURVEY.md A.6]: ``VSampler``'s loop with ``num_resamples`` evaluations
+    per step; after each one the region where ``mask`` is True is replaced by the source re-noised to the iteration's level.  The whole
+    loop runs inside ``sf_vinpaint``.  The noise is the device's counter-based generator (``philox_normal``), keyed by ``seed``; with
+    ``seed=None`` one seed is drawn from torch's CPU generator, so ``torch.manual_seed`` makes a run repeatable."""
+
+    diffusion_types = [VDiffusion]
+
+    def __init__(self, net: nn.Module, schedule: Optional[nn.Module] = None, use_graph: bool = True):
+        super().__init__()
+        object.__setattr__(self, "_net", net)
+        self.schedule = schedule if schedule is not None else LinearSchedule()
+        self.use_graph = use_graph
+
+    @property
+    def net(self):
+        return self._net
+
+    @torch.no_grad()
+    def forward(self, source: Tensor, mask: Tensor, num_steps: int, num_resamples: int, show_progress: bool = False,
+                x_noisy: Optional[Tensor] = None, *, seed: Optional[int] = None, embedding: Optional[Tensor] = None,
+                channels: Optional[Sequence[Tensor]] = None, embedding_scale: float = 1.0, **kwargs) -> Tensor:
+        if kwargs:
+            raise TypeError(f"unsupported sampling arguments: {sorted(kwargs)}")
+        if not isinstance(self.schedule, LinearSchedule) or (self.schedule.start, self.schedule.end) != (1.0, 0.0):
+            raise NotImplementedError("only LinearSchedule(1 -> 0) (the audio_diffusion_pytorch default) is implemented")
+        assert embedding is not None, "ClassifierFreeGuidancePlugin requires embedding"
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        return self._net.engine().inpaint(source, mask, num_steps, num_resamples, channels, embedding, embedding_scale,
+                                          x_noisy=x_noisy, seed=seed, use_graph=self.use_graph)
+
+
 class DiffusionModel(nn.Module):
     """``audio_diffusion_pytorch.DiffusionModel``: routes ``diffusion_*`` / ``sampler_*`` kwargs, the rest builds the net."""
 
@@ -318,3 +369,19 @@ class DiffusionModel(nn.Module):
     @torch.no_grad()
     def sample(self, *args, **kwargs) -> Tensor:
         return self.sampler(*args, **kwargs)
+
+    @property
+    def inpainter(self) -> "VInpainter":
+        """The ``VInpainter`` behind ``inpaint``, built on first use: it holds no state of its own, so the constructor and the
+        checkpoint layout are what they were."""
+        inpainter = self.__dict__.get("_inpainter")
+        if inpainter is None:
+            inpainter = VInpainter(net=self.net, use_graph=getattr(self.sampler, "use_graph", True))
+            object.__setattr__(self, "_inpainter", inpainter)
+        return inpainter
+
+    @torch.no_grad()
+    def inpaint(self, *args, **kwargs) -> Tensor:
+        """``VInpainter(net)(source, mask, num_steps, num_resamples, ...)``: regenerate where ``mask`` is False, keep the source
+        where it is True."""
+        return self.inpainter(*args, **kwargs)

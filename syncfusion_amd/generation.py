@@ -53,6 +53,130 @@ def generate_batch(model, y: Tensor, z: Optional[Tensor] = None, text: Optional[
     return gen[:, :, : (cut_length or length)]                                     # :91,100
 
 
+def regions_to_keep_mask(regions, B: int, L: int) -> Tensor:
+    """``regions`` -> the bool keep mask ``(B, 1, L)`` (CPU) of ``inpaint_batch``: True = keep the source, False = regenerate.
+    ``regions`` is a list of ``(start, end)`` sample ranges (end exclusive) to regenerate in every clip, or a list of ``B`` such lists, one
+    per clip.  Ranges may be empty, touch or overlap; each must satisfy ``0 <= start <= end <= L``.  No ranges: everything is kept."""
+    regions = list(regions)
+    per_clip = len(regions) > 0 and all(isinstance(r, (list, tuple)) and (len(r) == 0 or isinstance(r[0], (list, tuple))) for r in regions)
+    if per_clip:
+        if len(regions) != B:
+            raise ValueError(f"per-clip regions: expected {B} lists, got {len(regions)}")
+        clips = [list(r) for r in regions]
+    else:
+        clips = [regions] * B
+    keep = torch.ones((B, 1, L), dtype=torch.bool)
+    for b, rs in enumerate(clips):
+        for r in rs:
+            if not isinstance(r, (list, tuple)) or len(r) != 2:
+                raise ValueError(f"a region is a (start, end) pair, got {r!r}")
+            start, end = int(r[0]), int(r[1])
+            if not 0 <= start <= end <= L:
+                raise ValueError(f"region ({start}, {end}) is not inside [0, {L}] with start <= end")
+            keep[b, :, start:end] = False
+    return keep
+
+
+def _embed(model, z, text, cond_text: bool, device) -> Tensor:
+    if cond_text:
+        return model.clap_encode_text(list(text)).to(device)
+    return model.clap_encode_audio(z.to(device)).to(device)
+
+
+def _draw_seed(seed: Optional[int]) -> int:
+    return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+
+
+@torch.no_grad()
+def inpaint_batch(model, audio: Tensor, y: Tensor, z: Optional[Tensor] = None, text: Optional[Sequence[str]] = None, *,
+                  regions=None, keep_mask: Optional[Tensor] = None, num_steps: int = 150, num_resamples: int = 4,
+                  embedding_scale: float = 7.5, cond_text: bool = False, seed: Optional[int] = None, noise: Optional[Tensor] = None,
+                  generator: Optional[torch.Generator] = None) -> Tensor:
+    """``generate_batch`` with a source: regenerates parts of ``audio`` ``(B, 1, L)`` under the same onset track ``y`` and CLAP
+    conditioning and keeps the rest bit for bit.  Exactly one of ``regions`` (``(start, end)`` sample ranges to REGENERATE, for the
+    batch or per clip: ``regions_to_keep_mask``) and ``keep_mask`` (bool, True = keep, ``audio``'s shape or broadcastable to it).
+
+    ``num_resamples=4`` is an UNVALIDATED default (no listening test was possible): RePaint (Lugmayr et al., CVPR 2022, section 4.2 and
+    table 3) finds that re-noising and denoising again at one level is what makes the regenerated part agree with the kept one, with
+    most of the gain in the first few resamples; each costs a full U-Net evaluation, so a call costs ``num_resamples`` x ``sample()``.
+    ``seed`` keys the device noise of the kept region (``None``: drawn from torch's CPU generator); ``noise`` / ``generator``: the
+    start noise, as in ``generate_batch``."""
+    if (regions is None) == (keep_mask is None):
+        raise ValueError("exactly one of `regions` and `keep_mask` must be given")
+    device = model.device
+    _lib.require_gpu_tensor(torch.empty(0, device=device), "inpaint_batch")
+    if audio.dim() != 3:
+        raise ValueError(f"audio must be (B, 1, L), got shape {tuple(audio.shape)}")
+    B, _, L = audio.shape
+    if keep_mask is None:
+        keep_mask = regions_to_keep_mask(regions, B, L)
+    if noise is None:
+        noise = torch.randn(tuple(audio.shape), device=device, generator=generator)
+    y = y.to(device)
+    _, y_latent = model.onsets_encoder(y, with_info=True)
+    z_latent = _embed(model, z, text, cond_text, device)
+    return model.model.inpaint(audio.to(device), keep_mask.to(device), num_steps, num_resamples, x_noisy=noise.to(device),
+                               seed=_draw_seed(seed), channels=y_latent["xs"][2:-1], embedding=z_latent, embedding_scale=embedding_scale)
+
+
+def long_windows(total: int, length: int, overlap: int) -> List[tuple]:
+    """Windows of ``length`` samples that cover ``total`` with at least ``overlap`` samples shared between neighbours (pure host
+    function): starts 0, hop, 2 hop, ... with hop = length - overlap while start + length < total, then a last window at
+    total - length.  Returns ``[(start, kept_prefix)]``, kept_prefix = end of the previous window - start (0 for the first)."""
+    total, length, overlap = int(total), int(length), int(overlap)
+    if not 0 < overlap < length <= total:
+        raise ValueError(f"need 0 < overlap < length <= total, got overlap={overlap}, length={length}, total={total}")
+    hop = length - overlap
+    starts, start = [], 0
+    while start + length < total:
+        starts.append(start)
+        start += hop
+    starts.append(total - length)
+    out, prev_end = [], None
+    for st in starts:
+        out.append((st, 0 if prev_end is None else prev_end - st))
+        prev_end = st + length
+    return out
+
+
+@torch.no_grad()
+def generate_long(model, y: Tensor, z: Optional[Tensor] = None, text: Optional[Sequence[str]] = None, *, length: int = 2 ** 18,
+                  overlap: int = 2 ** 14, num_steps: int = 150, num_resamples: int = 4, embedding_scale: float = 7.5,
+                  cond_text: bool = False, seed: Optional[int] = None, generator: Optional[torch.Generator] = None) -> Tensor:
+    """A track longer than one window: ``y`` is ``(B, 1, total)`` and so is the result.  The CLAP embedding is computed once.  Window 0
+    (``long_windows``) comes from ``sample()``; window w > 0 from ``inpaint()`` with its first kept_prefix samples held to the previous
+    window's tail (mask True there), its own slice of ``y`` through the onset encoder and the noise seed ``seed + w``.  Joins are
+    sample-exact: no cross-fade.
+
+    UNVALIDATED defaults (no listening test was possible).  ``overlap=2**14`` (0.34 s at 48 kHz): the kept prefix is what tells the
+    new window which sound is ringing, so it should span the decay of a typical Foley hit; it costs 1/16 of every window's new
+    samples.  ``num_resamples=4``: see ``inpaint_batch``.  ``seed=None``: drawn from torch's CPU generator."""
+    device = model.device
+    _lib.require_gpu_tensor(torch.empty(0, device=device), "generate_long")
+    if y.dim() != 3:
+        raise ValueError(f"y must be (B, channels, total), got shape {tuple(y.shape)}")
+    B, total = y.shape[0], y.shape[2]
+    windows = long_windows(total, length, overlap)
+    seed = _draw_seed(seed)
+    y = y.to(device)
+    z_latent = _embed(model, z, text, cond_text, device)
+    out = torch.empty((B, 1, total), dtype=torch.float32, device=device)
+    for w, (start, kept) in enumerate(windows):
+        _, y_latent = model.onsets_encoder(y[:, :, start:start + length].contiguous(), with_info=True)
+        noise = torch.randn((B, 1, length), device=device, generator=generator)
+        cond = dict(channels=y_latent["xs"][2:-1], embedding=z_latent, embedding_scale=embedding_scale)
+        if w == 0:
+            win = model.model.sample(x_noisy=noise, num_steps=num_steps, **cond)
+        else:
+            source = torch.zeros((B, 1, length), dtype=torch.float32, device=device)
+            source[:, :, :kept] = out[:, :, start:start + kept]
+            mask = torch.zeros((B, 1, length), dtype=torch.bool, device=device)
+            mask[:, :, :kept] = True
+            win = model.model.inpaint(source, mask, num_steps, num_resamples, x_noisy=noise, seed=seed + w, **cond)
+        out[:, :, start:start + length] = win
+    return out
+
+
 def save_wav(path: Union[str, Path], audio: Tensor, sample_rate: int) -> None:
     """(channels, n) float tensor -> 32-bit IEEE-float wav, the file ``torchaudio.save(path, float32 tensor, rate)`` writes
     (main/generation.py:104-122): RIFF/WAVE, ``fmt `` with format tag 3 (WAVE_FORMAT_IEEE_FLOAT), the ``fact`` chunk non-PCM
