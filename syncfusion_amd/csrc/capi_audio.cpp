@@ -11,17 +11,6 @@
 
 using namespace sf;
 
-#define SF_API_BEGIN try {
-#define SF_API_END                  \
-  }                                 \
-  catch (const EngineError &e) {    \
-    return e.code;                  \
-  }                                 \
-  catch (const std::exception &e) { \
-    set_error("%s", e.what());      \
-    return SF_ERR_INVALID;          \
-  }
-
 struct sf_audio_features {
   AudioTables tab;                    // device pointers into `dev` once uploaded
   int win = 0;                        // uncentred handles (sf_audio_features_create_framed): window length <= n_fft
@@ -76,8 +65,7 @@ static int check_call(const sf_audio_features *h, const float *wav, int B, int L
   if (h->tab.pad_mode == AUDIO_PAD_REFLECT && L <= h->tab.n_fft / 2) fail(SF_ERR_SHAPE, "reflect padding needs L > n_fft / 2 (L = %d, n_fft = %d)", L, h->tab.n_fft);
   const int64_t T = audio_frames(L, h->tab.hop);
   if ((int64_t)B * h->tab.n_mels * T >= (1ll << 31) || (int64_t)B * L >= (1ll << 40)) fail(SF_ERR_SHAPE, "batch too large");
-  const int64_t need = audio_ws_bytes(h->tab.n_mels, h->tab.hop, B, L);
-  if (!ws || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  require_workspace(ws, ws_bytes, audio_ws_bytes(h->tab.n_mels, h->tab.hop, B, L));
   return (int)T;
 }
 

@@ -9,17 +9,6 @@
 
 using namespace sf;
 
-#define SF_API_BEGIN try {
-#define SF_API_END                  \
-  }                                 \
-  catch (const EngineError &e) {    \
-    return e.code;                  \
-  }                                 \
-  catch (const std::exception &e) { \
-    set_error("%s", e.what());      \
-    return SF_ERR_INVALID;          \
-  }
-
 extern "C" {
 
 const char *sf_version(void) { return "syncfusion_amd 0.1.0 (gfx950)"; }
@@ -118,8 +107,7 @@ int sf_frames_augment(const uint8_t *frames, int N, int T, int H, int W, int res
     }
     any_contrast = any_contrast || (c.mask & 2);
   }
-  const int64_t need = frames_augment_workspace_bytes(N, T, out_h, out_w);
-  if (!ws || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  require_workspace(ws, ws_bytes, frames_augment_workspace_bytes(N, T, out_h, out_w));
   hipError_t e = launch_frames_augment(frames, N, T, H, W, resize_h, resize_w, out_h, out_w, reinterpret_cast<const AugClip *>(table_dev), any_contrast, mean3,
                                        std3, out, static_cast<float *>(ws), static_cast<hipStream_t>(stream));
   if (e == hipErrorInvalidValue) fail(SF_ERR_UNSUPPORTED, "down-scaling factor above 7.5 (or more than 2^31 workgroups) is not supported");

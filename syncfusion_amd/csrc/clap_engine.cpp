@@ -15,17 +15,6 @@
 
 using namespace sf;
 
-#define SF_API_BEGIN try {
-#define SF_API_END                  \
-  }                                 \
-  catch (const EngineError &e) {    \
-    return e.code;                  \
-  }                                 \
-  catch (const std::exception &e) { \
-    set_error("%s", e.what());      \
-    return SF_ERR_INVALID;          \
-  }
-
 namespace {
 
 constexpr int PATCH = 4;
@@ -39,13 +28,6 @@ struct StageW {
   int res = 0, C = 0, heads = 0;       // tokens per side, width
   std::vector<BlockW> blocks;
   float *merge_w = nullptr, *merge_b = nullptr;
-};
-
-// one GEMM of the network on `tokens` rows per clip
-struct Gemm {
-  std::string name;
-  int tokens, K, N, act;
-  bool res;
 };
 
 void check_config(const sf_clap_audio_config &c) {
@@ -72,50 +54,23 @@ void check_config(const sf_clap_audio_config &c) {
 
 int shift_of(const sf_clap_audio_config &c, int res, int j) { return (res <= c.window || (j % 2) == 0) ? 0 : c.window / 2; }
 
-std::vector<Gemm> gemms_of(const sf_clap_audio_config &c) {
-  std::vector<Gemm> g;
+// the GEMMs of the network at B clips
+std::vector<LinearDesc> gemms_of(const sf_clap_audio_config &c, int B) {
+  std::vector<LinearDesc> g;
   int res = c.spec_size / PATCH;
   for (int i = 0; i < c.n_stages; ++i) {
     const int C = c.embed_dim << i, tok = res * res;
     const std::string st = "stage " + std::to_string(i) + " ";
-    g.push_back({st + "qkv", tok, C, 3 * C, 0, false});
-    g.push_back({st + "proj", tok, C, C, 0, true});
-    g.push_back({st + "fc1", tok, C, c.mlp_ratio * C, 2, false});
-    g.push_back({st + "fc2", tok, c.mlp_ratio * C, C, 0, true});
+    g.push_back({st + "qkv", B, tok, C, 3 * C, 0, false});
+    g.push_back({st + "proj", B, tok, C, C, 0, true});
+    g.push_back({st + "fc1", B, tok, C, c.mlp_ratio * C, 2, false});
+    g.push_back({st + "fc2", B, tok, c.mlp_ratio * C, C, 0, true});
     if (i + 1 < c.n_stages) {
-      g.push_back({st + "merge", tok / 4, 4 * C, 2 * C, 0, false});
+      g.push_back({st + "merge", B, tok / 4, 4 * C, 2 * C, 0, false});
       res /= 2;
     }
   }
   return g;
-}
-
-ConvGemmArgs lin(const float *src, int B, int tokens, int K, int N, const float *w, const float *bias, const float *res, int act, float *out) {
-  ConvGemmArgs a;
-  a.src = src;
-  a.src_ld = K;
-  a.w = w;
-  a.bias = bias;
-  a.N = N;
-  a.K = K;
-  a.cin = K;
-  a.taps = 1;
-  a.M = B * tokens;
-  a.Lout = a.Lsrc = tokens;
-  a.out = out;
-  a.out_ld = N;
-  a.n_store = N;
-  a.res = res;
-  a.res_ld = N;
-  a.act = act;
-  a.solo = 1;
-  return a;
-}
-
-// what the plan needs is whether a pointer is set, not where it points
-alignas(16) float g_some[4];
-ConvGemmPlan plan_of(const Gemm &g, int B) {
-  return conv_gemm_plan(F32, lin(g_some, B, g.tokens, g.K, g.N, g_some, g_some, g.res ? g_some : nullptr, g.act, g_some));
 }
 
 }  // namespace
@@ -153,20 +108,14 @@ int sf_clap_audio_create(const sf_clap_audio_config *cfg, const sf_tensor *weigh
   const sf_clap_audio_config c = *cfg;
   check_config(c);
   const WeightMap wm(weights, n_weights);
-  // every name and size is looked up before anything is allocated or copied: refusals come before the first HIP call
-  struct Want {
-    std::string name;
-    int64_t n;
-    float **dst;
-  };
-  std::vector<Want> want;
+  WeightWants ww;
   auto eng = std::unique_ptr<sf_clap_audio>(new sf_clap_audio());
   eng->cfg = c;
   const int E = c.embed_dim, J = c.joint_dim, NBIAS = (2 * c.window - 1) * (2 * c.window - 1);
-  want.push_back({"patch.w", (int64_t)E * PATCH * PATCH, &eng->patch_w});
-  want.push_back({"patch.b", E, &eng->patch_b});
-  want.push_back({"patch.g", E, &eng->patch_g});
-  want.push_back({"patch.beta", E, &eng->patch_beta});
+  ww.want("patch.w", (int64_t)E * PATCH * PATCH, &eng->patch_w);
+  ww.want("patch.b", E, &eng->patch_b);
+  ww.want("patch.g", E, &eng->patch_g);
+  ww.want("patch.beta", E, &eng->patch_beta);
   eng->stages.resize(c.n_stages);
   int res = c.spec_size / PATCH;
   eng->tokens0 = res * res;
@@ -179,38 +128,33 @@ int sf_clap_audio_create(const sf_clap_audio_config *cfg, const sf_tensor *weigh
       BlockW &b = st.blocks[j];
       b.shift = shift_of(c, res, j);
       const std::string p = "s" + std::to_string(i) + ".b" + std::to_string(j) + ".";
-      want.push_back({p + "qkv.w", 3 * C * C, &b.qkv_w});
-      want.push_back({p + "qkv.b", 3 * C, &b.qkv_b});
-      want.push_back({p + "rpb", (int64_t)NBIAS * st.heads, &b.rpb});
-      want.push_back({p + "proj.w", C * C, &b.proj_w});
-      want.push_back({p + "proj.b", C, &b.proj_b});
-      want.push_back({p + "fc1.w", Hd * C, &b.fc1_w});
-      want.push_back({p + "fc1.b", Hd, &b.fc1_b});
-      want.push_back({p + "fc2.w", C * Hd, &b.fc2_w});
-      want.push_back({p + "fc2.b", C, &b.fc2_b});
+      ww.want(p + "qkv.w", 3 * C * C, &b.qkv_w);
+      ww.want(p + "qkv.b", 3 * C, &b.qkv_b);
+      ww.want(p + "rpb", (int64_t)NBIAS * st.heads, &b.rpb);
+      ww.want(p + "proj.w", C * C, &b.proj_w);
+      ww.want(p + "proj.b", C, &b.proj_b);
+      ww.want(p + "fc1.w", Hd * C, &b.fc1_w);
+      ww.want(p + "fc1.b", Hd, &b.fc1_b);
+      ww.want(p + "fc2.w", C * Hd, &b.fc2_w);
+      ww.want(p + "fc2.b", C, &b.fc2_b);
     }
     if (i + 1 < c.n_stages) {
       const std::string p = "s" + std::to_string(i) + ".merge.";
-      want.push_back({p + "w", 2 * C * 4 * C, &st.merge_w});
-      want.push_back({p + "b", 2 * C, &st.merge_b});
+      ww.want(p + "w", 2 * C * 4 * C, &st.merge_w);
+      ww.want(p + "b", 2 * C, &st.merge_b);
       res /= 2;
     }
   }
   eng->final_C = eng->stages.back().C;
   eng->final_tokens = res * res;
-  want.push_back({"head.g", eng->final_C, &eng->head_g});
-  want.push_back({"head.beta", eng->final_C, &eng->head_beta});
-  want.push_back({"proj0.w", (int64_t)J * eng->final_C, &eng->p0_w});
-  want.push_back({"proj0.b", J, &eng->p0_b});
-  want.push_back({"proj2.w", (int64_t)J * J, &eng->p2_w});
-  want.push_back({"proj2.b", J, &eng->p2_b});
-  for (const Want &w : want) (void)wm.get(w.name, w.n);
-
+  ww.want("head.g", eng->final_C, &eng->head_g);
+  ww.want("head.beta", eng->final_C, &eng->head_beta);
+  ww.want("proj0.w", (int64_t)J * eng->final_C, &eng->p0_w);
+  ww.want("proj0.b", J, &eng->p0_b);
+  ww.want("proj2.w", (int64_t)J * J, &eng->p2_w);
+  ww.want("proj2.b", J, &eng->p2_b);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  for (const Want &w : want) {
-    *w.dst = eng->arena.alloc_n<float>(w.n);
-    SF_HIP(hipMemcpyAsync(*w.dst, wm.get(w.name, w.n), (size_t)w.n * 4, hipMemcpyDeviceToDevice, s));
-  }
+  ww.load(wm, eng->arena, s);   // refuses a missing or mis-sized name before the first HIP call
   SF_HIP(hipStreamSynchronize(s));
   *out = eng.release();
   return SF_OK;
@@ -231,14 +175,7 @@ int sf_clap_audio_describe(const sf_clap_audio_config *cfg, int B, char *text, i
   if (!cfg || !text || capacity < 1) fail(SF_ERR_INVALID, "null argument");
   if (B < 1) fail(SF_ERR_INVALID, "B must be at least 1");
   check_config(*cfg);
-  std::string s;
-  for (const Gemm &g : gemms_of(*cfg)) {
-    char line[256];
-    snprintf(line, sizeof line, "%s: M %lld N %d K %d -> %s\n", g.name.c_str(), (long long)B * g.tokens, g.N, g.K, plan_of(g, B).label);
-    s += line;
-  }
-  if ((int64_t)s.size() + 1 > capacity) fail(SF_ERR_INVALID, "text capacity %lld below %lld", (long long)capacity, (long long)s.size() + 1);
-  memcpy(text, s.c_str(), s.size() + 1);
+  describe_gemms(gemms_of(*cfg, B), "", text, capacity);
   return SF_OK;
   SF_API_END
 }
@@ -249,44 +186,38 @@ int sf_clap_audio_forward(sf_clap_audio *h, const float *image, int B, float *em
   if (!h || !image || !embedding) fail(SF_ERR_INVALID, "null argument");
   if (B < 1) fail(SF_ERR_INVALID, "B must be at least 1");
   if (B > max_batch(h)) fail(SF_ERR_SHAPE, "at most %d clips per call", max_batch(h));
-  const int64_t need = ws_bytes_for(h, B);
-  if (!ws || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  require_workspace(ws, ws_bytes, ws_bytes_for(h, B));
   const sf_clap_audio_config &c = h->cfg;
-  for (const Gemm &g : gemms_of(c))
-    if (plan_of(g, B).family == CG_INVALID) fail(SF_ERR_UNSUPPORTED, "%s (M %lld, N %d, K %d): no GEMM kernel takes the shape", g.name.c_str(),
-                                                 (long long)B * g.tokens, g.N, g.K);
+  require_gemm_kernels(gemms_of(c, B));
   hipStream_t s = static_cast<hipStream_t>(stream);
   Workspace wsp(ws, ws_bytes);
   const int64_t unit = (int64_t)B * h->tokens0 * c.embed_dim;
   float *x = wsp.alloc_n<float>(unit), *x1 = wsp.alloc_n<float>(unit), *t = wsp.alloc_n<float>(unit), *att = wsp.alloc_n<float>(unit);
   float *qkv = wsp.alloc_n<float>(3 * unit), *hid = wsp.alloc_n<float>(c.mlp_ratio * unit);
   float *tail = wsp.alloc_n<float>((int64_t)B * (h->final_C + 2 * c.joint_dim));
-  auto tap = [&](int i, const float *src, int64_t floats) {
-    if (taps && taps[i]) SF_HIP(hipMemcpyAsync(taps[i], src, (size_t)floats * 4, hipMemcpyDeviceToDevice, s));
-  };
   SF_HIP(launch_patch_embed(image, B, c.spec_size, c.embed_dim, h->patch_w, h->patch_b, h->patch_g, h->patch_beta, c.ln_eps, x, s));
-  tap(0, x, unit);
+  copy_tap(taps, 0, x, unit, s);
   for (int i = 0; i < c.n_stages; ++i) {
     const StageW &st = h->stages[i];
     const int C = st.C, tok = st.res * st.res, Hd = c.mlp_ratio * C;
     const int64_t M = (int64_t)B * tok;
     for (const BlockW &b : st.blocks) {
       SF_HIP(launch_swin_layernorm(x, M, C, c.ln_eps, 0, 0, 0, t, s));
-      SF_HIP(launch_conv_gemm(F32, lin(t, B, tok, C, 3 * C, b.qkv_w, b.qkv_b, nullptr, 0, qkv), s));
+      SF_HIP(launch_conv_gemm(F32, token_linear_args(t, B, tok, C, 3 * C, b.qkv_w, b.qkv_b, nullptr, 0, qkv), s));
       SF_HIP(launch_window_attention(qkv, B, st.res, st.res, C, st.heads, b.shift, b.rpb, c.mask_value, att, s));
-      SF_HIP(launch_conv_gemm(F32, lin(att, B, tok, C, C, b.proj_w, b.proj_b, x, 0, x1), s));
+      SF_HIP(launch_conv_gemm(F32, token_linear_args(att, B, tok, C, C, b.proj_w, b.proj_b, x, 0, x1), s));
       SF_HIP(launch_swin_layernorm(x1, M, C, c.ln_eps, 0, 0, 0, t, s));
-      SF_HIP(launch_conv_gemm(F32, lin(t, B, tok, C, Hd, b.fc1_w, b.fc1_b, nullptr, 2, hid), s));
-      SF_HIP(launch_conv_gemm(F32, lin(hid, B, tok, Hd, C, b.fc2_w, b.fc2_b, x1, 0, x), s));
+      SF_HIP(launch_conv_gemm(F32, token_linear_args(t, B, tok, C, Hd, b.fc1_w, b.fc1_b, nullptr, 2, hid), s));
+      SF_HIP(launch_conv_gemm(F32, token_linear_args(hid, B, tok, Hd, C, b.fc2_w, b.fc2_b, x1, 0, x), s));
     }
     int64_t floats = M * C;
     if (i + 1 < c.n_stages) {
       SF_HIP(launch_swin_layernorm(x, M / 4, 4 * C, c.ln_eps, 1, st.res, st.res, t, s));
-      SF_HIP(launch_conv_gemm(F32, lin(t, B, tok / 4, 4 * C, 2 * C, st.merge_w, st.merge_b, nullptr, 0, x1), s));
+      SF_HIP(launch_conv_gemm(F32, token_linear_args(t, B, tok / 4, 4 * C, 2 * C, st.merge_w, st.merge_b, nullptr, 0, x1), s));
       std::swap(x, x1);
       floats /= 2;
     }
-    tap(i + 1, x, floats);
+    copy_tap(taps, i + 1, x, floats, s);
   }
   SF_HIP(launch_clap_tail(x, B, h->final_tokens, h->final_C, c.joint_dim, h->head_g, h->head_beta, c.ln_eps, h->p0_w, h->p0_b, h->p2_w, h->p2_b,
                           c.projection_relu, c.normalize, tail, embedding, s));

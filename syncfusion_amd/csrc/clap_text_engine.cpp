@@ -14,29 +14,11 @@
 
 using namespace sf;
 
-#define SF_API_BEGIN try {
-#define SF_API_END                  \
-  }                                 \
-  catch (const EngineError &e) {    \
-    return e.code;                  \
-  }                                 \
-  catch (const std::exception &e) { \
-    set_error("%s", e.what());      \
-    return SF_ERR_INVALID;          \
-  }
-
 namespace {
 
 struct LayerW {
   float *qkv_w = nullptr, *qkv_b = nullptr, *ao_w = nullptr, *ao_b = nullptr, *ln1_g = nullptr, *ln1_b = nullptr;
   float *fc1_w = nullptr, *fc1_b = nullptr, *fc2_w = nullptr, *fc2_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
-};
-
-// one GEMM of a layer on S rows per text
-struct Gemm {
-  const char *name;
-  int K, N, act;
-  bool res;
 };
 
 void check_config(const sf_clap_text_config &c) {
@@ -62,37 +44,11 @@ void check_length(const sf_clap_text_config &c, int S) {
   if (S + c.pad_id + 1 > c.max_positions) fail(SF_ERR_SHAPE, "S = %d needs %d position rows, the table has %d", S, S + c.pad_id + 1, c.max_positions);
 }
 
-std::vector<Gemm> gemms_of(const sf_clap_text_config &c) {
+// the GEMMs of one layer at B texts of S tokens
+std::vector<LinearDesc> gemms_of(const sf_clap_text_config &c, int B, int S) {
   const int C = c.hidden, I = c.intermediate;
-  return {{"qkv", C, 3 * C, 0, false}, {"attention output", C, C, 0, true}, {"intermediate", C, I, 2, false}, {"output", I, C, 0, true}};
-}
-
-ConvGemmArgs lin(const float *src, int B, int S, int K, int N, const float *w, const float *bias, const float *res, int act, float *out) {
-  ConvGemmArgs a;
-  a.src = src;
-  a.src_ld = K;
-  a.w = w;
-  a.bias = bias;
-  a.N = N;
-  a.K = K;
-  a.cin = K;
-  a.taps = 1;
-  a.M = B * S;
-  a.Lout = a.Lsrc = S;
-  a.out = out;
-  a.out_ld = N;
-  a.n_store = N;
-  a.res = res;
-  a.res_ld = N;
-  a.act = act;
-  a.solo = 1;
-  return a;
-}
-
-// what the plan needs is whether a pointer is set, not where it points
-alignas(16) float g_some[4];
-ConvGemmPlan plan_of(const Gemm &g, int B, int S) {
-  return conv_gemm_plan(F32, lin(g_some, B, S, g.K, g.N, g_some, g_some, g.res ? g_some : nullptr, g.act, g_some));
+  return {{"qkv", B, S, C, 3 * C, 0, false}, {"attention output", B, S, C, C, 0, true}, {"intermediate", B, S, C, I, 2, false},
+          {"output", B, S, I, C, 0, true}};
 }
 
 // the widest activation (the intermediate rows, or q | k | v) stays below 2^31 bytes: the GEMM kernels' 32-bit offsets
@@ -126,53 +82,42 @@ int sf_clap_text_create(const sf_clap_text_config *cfg, const sf_tensor *weights
   const sf_clap_text_config c = *cfg;
   check_config(c);
   const WeightMap wm(weights, n_weights);
-  // every name and size is looked up before anything is allocated or copied: refusals come before the first HIP call
-  struct Want {
-    std::string name;
-    int64_t n;
-    float **dst;
-  };
-  std::vector<Want> want;
+  WeightWants ww;
   auto eng = std::unique_ptr<sf_clap_text>(new sf_clap_text());
   eng->cfg = c;
   const int64_t C = c.hidden, I = c.intermediate, J = c.joint_dim;
-  want.push_back({"emb.word", (int64_t)c.vocab_size * C, &eng->word});
-  want.push_back({"emb.pos", (int64_t)c.max_positions * C, &eng->pos});
-  want.push_back({"emb.type", C, &eng->type});
-  want.push_back({"emb.g", C, &eng->emb_g});
-  want.push_back({"emb.beta", C, &eng->emb_b});
+  ww.want("emb.word", (int64_t)c.vocab_size * C, &eng->word);
+  ww.want("emb.pos", (int64_t)c.max_positions * C, &eng->pos);
+  ww.want("emb.type", C, &eng->type);
+  ww.want("emb.g", C, &eng->emb_g);
+  ww.want("emb.beta", C, &eng->emb_b);
   eng->layers.resize(c.layers);
   for (int i = 0; i < c.layers; ++i) {
     LayerW &l = eng->layers[i];
     const std::string p = "l" + std::to_string(i) + ".";
-    want.push_back({p + "qkv.w", 3 * C * C, &l.qkv_w});
-    want.push_back({p + "qkv.b", 3 * C, &l.qkv_b});
-    want.push_back({p + "ao.w", C * C, &l.ao_w});
-    want.push_back({p + "ao.b", C, &l.ao_b});
-    want.push_back({p + "ln1.g", C, &l.ln1_g});
-    want.push_back({p + "ln1.beta", C, &l.ln1_b});
-    want.push_back({p + "fc1.w", I * C, &l.fc1_w});
-    want.push_back({p + "fc1.b", I, &l.fc1_b});
-    want.push_back({p + "fc2.w", C * I, &l.fc2_w});
-    want.push_back({p + "fc2.b", C, &l.fc2_b});
-    want.push_back({p + "ln2.g", C, &l.ln2_g});
-    want.push_back({p + "ln2.beta", C, &l.ln2_b});
+    ww.want(p + "qkv.w", 3 * C * C, &l.qkv_w);
+    ww.want(p + "qkv.b", 3 * C, &l.qkv_b);
+    ww.want(p + "ao.w", C * C, &l.ao_w);
+    ww.want(p + "ao.b", C, &l.ao_b);
+    ww.want(p + "ln1.g", C, &l.ln1_g);
+    ww.want(p + "ln1.beta", C, &l.ln1_b);
+    ww.want(p + "fc1.w", I * C, &l.fc1_w);
+    ww.want(p + "fc1.b", I, &l.fc1_b);
+    ww.want(p + "fc2.w", C * I, &l.fc2_w);
+    ww.want(p + "fc2.b", C, &l.fc2_b);
+    ww.want(p + "ln2.g", C, &l.ln2_g);
+    ww.want(p + "ln2.beta", C, &l.ln2_b);
   }
   if (c.pooling == 0) {
-    want.push_back({"pool.w", C * C, &eng->pool_w});
-    want.push_back({"pool.b", C, &eng->pool_b});
+    ww.want("pool.w", C * C, &eng->pool_w);
+    ww.want("pool.b", C, &eng->pool_b);
   }
-  want.push_back({"proj0.w", J * C, &eng->p0_w});
-  want.push_back({"proj0.b", J, &eng->p0_b});
-  want.push_back({"proj2.w", J * J, &eng->p2_w});
-  want.push_back({"proj2.b", J, &eng->p2_b});
-  for (const Want &w : want) (void)wm.get(w.name, w.n);
-
+  ww.want("proj0.w", J * C, &eng->p0_w);
+  ww.want("proj0.b", J, &eng->p0_b);
+  ww.want("proj2.w", J * J, &eng->p2_w);
+  ww.want("proj2.b", J, &eng->p2_b);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  for (const Want &w : want) {
-    *w.dst = eng->arena.alloc_n<float>(w.n);
-    SF_HIP(hipMemcpyAsync(*w.dst, wm.get(w.name, w.n), (size_t)w.n * 4, hipMemcpyDeviceToDevice, s));
-  }
+  ww.load(wm, eng->arena, s);   // refuses a missing or mis-sized name before the first HIP call
   SF_HIP(hipStreamSynchronize(s));
   *out = eng.release();
   return SF_OK;
@@ -193,14 +138,7 @@ int sf_clap_text_describe(const sf_clap_text_config *cfg, int B, int S, char *te
   check_config(*cfg);
   check_length(*cfg, S);
   if ((int64_t)B * S > max_rows(*cfg)) fail(SF_ERR_SHAPE, "at most %lld token rows per call", (long long)max_rows(*cfg));
-  std::string s;
-  for (const Gemm &g : gemms_of(*cfg)) {
-    char line[256];
-    snprintf(line, sizeof line, "%s (x %d layers): M %lld N %d K %d -> %s\n", g.name, cfg->layers, (long long)B * S, g.N, g.K, plan_of(g, B, S).label);
-    s += line;
-  }
-  if ((int64_t)s.size() + 1 > capacity) fail(SF_ERR_INVALID, "text capacity %lld below %lld", (long long)capacity, (long long)s.size() + 1);
-  memcpy(text, s.c_str(), s.size() + 1);
+  describe_gemms(gemms_of(*cfg, B, S), " (x " + std::to_string(cfg->layers) + " layers)", text, capacity);
   return SF_OK;
   SF_API_END
 }
@@ -213,11 +151,8 @@ int sf_clap_text_forward(sf_clap_text *h, const int32_t *ids, const int32_t *mas
   const sf_clap_text_config &c = h->cfg;
   check_length(c, S);
   if ((int64_t)B * S > max_rows(c)) fail(SF_ERR_SHAPE, "at most %lld token rows per call", (long long)max_rows(c));
-  const int64_t need = ws_bytes_for(c, B, S);
-  if (!ws || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
-  for (const Gemm &g : gemms_of(c))
-    if (plan_of(g, B, S).family == CG_INVALID)
-      fail(SF_ERR_UNSUPPORTED, "%s (M %lld, N %d, K %d): no GEMM kernel takes the shape", g.name, (long long)B * S, g.N, g.K);
+  require_workspace(ws, ws_bytes, ws_bytes_for(c, B, S));
+  require_gemm_kernels(gemms_of(c, B, S));
   hipStream_t s = static_cast<hipStream_t>(stream);
   Workspace wsp(ws, ws_bytes);
   const int C = c.hidden, I = c.intermediate;
@@ -225,25 +160,22 @@ int sf_clap_text_forward(sf_clap_text *h, const int32_t *ids, const int32_t *mas
   float *x = wsp.alloc_n<float>(unit), *x1 = wsp.alloc_n<float>(unit), *t = wsp.alloc_n<float>(unit), *att = wsp.alloc_n<float>(unit);
   float *qkv = wsp.alloc_n<float>(3 * unit), *hid = wsp.alloc_n<float>(M * I);
   float *tail = wsp.alloc_n<float>((int64_t)B * (C + 2 * c.joint_dim));
-  auto tap = [&](int i, const float *src, int64_t floats) {
-    if (taps && taps[i]) SF_HIP(hipMemcpyAsync(taps[i], src, (size_t)floats * 4, hipMemcpyDeviceToDevice, s));
-  };
   SF_HIP(launch_text_embed(ids, B, S, C, c.vocab_size, c.max_positions, c.pad_id, h->word, h->pos, h->type, h->emb_g, h->emb_b, c.ln_eps, x, s));
-  tap(0, x, unit);
+  copy_tap(taps, 0, x, unit, s);
   for (int i = 0; i < c.layers; ++i) {
     const LayerW &l = h->layers[i];
-    SF_HIP(launch_conv_gemm(F32, lin(x, B, S, C, 3 * C, l.qkv_w, l.qkv_b, nullptr, 0, qkv), s));
+    SF_HIP(launch_conv_gemm(F32, token_linear_args(x, B, S, C, 3 * C, l.qkv_w, l.qkv_b, nullptr, 0, qkv), s));
     SF_HIP(launch_masked_attention(qkv, mask, B, S, c.heads, att, s));
-    SF_HIP(launch_conv_gemm(F32, lin(att, B, S, C, C, l.ao_w, l.ao_b, x, 0, t), s));
+    SF_HIP(launch_conv_gemm(F32, token_linear_args(att, B, S, C, C, l.ao_w, l.ao_b, x, 0, t), s));
     SF_HIP(launch_layernorm_affine(t, M, C, l.ln1_g, l.ln1_b, c.ln_eps, x1, s));
-    SF_HIP(launch_conv_gemm(F32, lin(x1, B, S, C, I, l.fc1_w, l.fc1_b, nullptr, 2, hid), s));
-    SF_HIP(launch_conv_gemm(F32, lin(hid, B, S, I, C, l.fc2_w, l.fc2_b, x1, 0, t), s));
+    SF_HIP(launch_conv_gemm(F32, token_linear_args(x1, B, S, C, I, l.fc1_w, l.fc1_b, nullptr, 2, hid), s));
+    SF_HIP(launch_conv_gemm(F32, token_linear_args(hid, B, S, I, C, l.fc2_w, l.fc2_b, x1, 0, t), s));
     SF_HIP(launch_layernorm_affine(t, M, C, l.ln2_g, l.ln2_b, c.ln_eps, x, s));
-    tap(i + 1, x, unit);
+    copy_tap(taps, i + 1, x, unit, s);
   }
   SF_HIP(launch_text_tail(x, B, S, C, c.joint_dim, c.pooling == 0, h->pool_w, h->pool_b, h->p0_w, h->p0_b, c.projection_relu, h->p2_w, h->p2_b,
                           c.normalize, tail, embedding, s));
-  tap(c.layers + 1, tail, (int64_t)B * C);
+  copy_tap(taps, c.layers + 1, tail, (int64_t)B * C, s);
   return SF_OK;
   SF_API_END
 }

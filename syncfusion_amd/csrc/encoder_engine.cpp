@@ -153,17 +153,6 @@ struct EncExec {
 
 }  // namespace
 
-#define SF_API_BEGIN try {
-#define SF_API_END                  \
-  }                                 \
-  catch (const EngineError &e) {    \
-    return e.code;                  \
-  }                                 \
-  catch (const std::exception &e) { \
-    set_error("%s", e.what());      \
-    return SF_ERR_INVALID;          \
-  }
-
 extern "C" {
 
 int sf_encoder1d_create(const sf_encoder1d_config *cfg, const sf_tensor *weights, int n_weights, void *stream, sf_encoder1d **out) {

@@ -43,6 +43,37 @@ const float *WeightMap::get(const std::string &name, int64_t numel) const {
   return static_cast<const float *>(it->second.first);
 }
 
+void WeightWants::load(const WeightMap &wm, DeviceArena &arena, hipStream_t s) const {
+  for (const Want &w : list_) (void)wm.get(w.name, w.n);
+  for (const Want &w : list_) {
+    *w.dst = arena.alloc_n<float>(w.n);
+    SF_HIP(hipMemcpyAsync(*w.dst, wm.get(w.name, w.n), (size_t)w.n * 4, hipMemcpyDeviceToDevice, s));
+  }
+}
+
+ConvGemmPlan plan_linear(const LinearDesc &g) {
+  // what the plan needs is whether a pointer is set, not where it points
+  alignas(16) static float some[4];
+  return conv_gemm_plan(F32, token_linear_args(some, g.items, g.tokens, g.K, g.N, some, some, g.res ? some : nullptr, g.act, some));
+}
+
+void require_gemm_kernels(const std::vector<LinearDesc> &list) {
+  for (const LinearDesc &g : list)
+    if (plan_linear(g).family == CG_INVALID)
+      fail(SF_ERR_UNSUPPORTED, "%s (M %lld, N %d, K %d): no GEMM kernel takes the shape", g.name.c_str(), g.rows(), g.N, g.K);
+}
+
+void describe_gemms(const std::vector<LinearDesc> &list, const std::string &suffix, char *text, int64_t capacity) {
+  std::string s;
+  for (const LinearDesc &g : list) {
+    char line[256];
+    snprintf(line, sizeof line, "%s%s: M %lld N %d K %d -> %s\n", g.name.c_str(), suffix.c_str(), g.rows(), g.N, g.K, plan_linear(g).label);
+    s += line;
+  }
+  if ((int64_t)s.size() + 1 > capacity) fail(SF_ERR_INVALID, "text capacity %lld below %lld", (long long)capacity, (long long)s.size() + 1);
+  memcpy(text, s.c_str(), s.size() + 1);
+}
+
 DeviceArena::~DeviceArena() {
   for (void *p : chunks_) (void)hipFree(p);
 }

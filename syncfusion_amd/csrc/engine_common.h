@@ -1,5 +1,6 @@
-// Host-side plumbing shared by the engines behind the C ABI: error reporting, named-weight lookup,
-// a device arena for packed weights and a bump allocator over the caller's workspace.
+// Host-side plumbing shared by the engines behind the C ABI: error reporting and the entry points' exception guard, named-weight lookup
+// and loading, a device arena for packed weights, a bump allocator over the caller's workspace, the ConvGemmArgs builders (gemm_args.h)
+// and the description / pre-flight of an engine's list of Linears.  A new engine starts from these, not from a copy of another engine.
 #pragma once
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -7,11 +8,13 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <exception>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/syncfusion_amd.h"
+#include "gemm_args.h"
 #include "kernels.h"
 
 namespace sf {
@@ -30,6 +33,18 @@ struct EngineError {
     hipError_t _e = (expr);                                                                 \
     if (_e != hipSuccess) ::sf::fail(SF_ERR_HIP, "%s -> %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
   } while (0)
+
+// The guard of every extern "C" entry point that can fail: the body runs between the two, and what it throws becomes the return code.
+#define SF_API_BEGIN try {
+#define SF_API_END                        \
+  }                                       \
+  catch (const ::sf::EngineError &e) {    \
+    return e.code;                        \
+  }                                       \
+  catch (const std::exception &e) {       \
+    ::sf::set_error("%s", e.what());      \
+    return SF_ERR_INVALID;                \
+  }
 
 inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
@@ -78,6 +93,49 @@ class Workspace {
   char *base_;
   int64_t cap_, used_ = 0;
 };
+
+// What follows is internal to the library: hidden, so that the list of exported symbols stays the C ABI's plus what it was.
+#pragma GCC visibility push(hidden)
+
+// The named fp32 parameters an engine keeps a device copy of, in the order it wants them laid out in its arena.
+class WeightWants {
+ public:
+  void want(std::string name, int64_t n, float **dst) { list_.push_back({std::move(name), n, dst}); }
+  // Looks up every name and size first -- every refusal comes before the first allocation or HIP call -- then allocates and copies in list
+  // order.  The copies are asynchronous on s: the caller synchronises.
+  void load(const WeightMap &wm, DeviceArena &arena, hipStream_t s) const;
+
+ private:
+  struct Want {
+    std::string name;
+    int64_t n;
+    float **dst;
+  };
+  std::vector<Want> list_;
+};
+
+// the caller's workspace holds `need` bytes
+inline void require_workspace(const void *ws, int64_t ws_bytes, int64_t need) {
+  if (!ws || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+}
+// copies `floats` values to the caller's i-th tap buffer when the caller passed one
+inline void copy_tap(float *const *taps, int i, const float *src, int64_t floats, hipStream_t s) {
+  if (taps && taps[i]) SF_HIP(hipMemcpyAsync(taps[i], src, (size_t)floats * 4, hipMemcpyDeviceToDevice, s));
+}
+
+// One fp32 Linear of a token engine at a given batch: `items` items of `tokens` rows each (token_linear_args).
+struct LinearDesc {
+  std::string name;
+  int items, tokens, K, N, act;
+  bool res;
+  long long rows() const { return (long long)items * tokens; }
+};
+ConvGemmPlan plan_linear(const LinearDesc &g);                  // what launch_conv_gemm would run for it
+void require_gemm_kernels(const std::vector<LinearDesc> &list);  // SF_ERR_UNSUPPORTED for the first entry no GEMM kernel takes
+// one line per entry, "<name><suffix>: M .. N .. K .. -> <kernel label>", into text (SF_ERR_INVALID when it does not fit)
+void describe_gemms(const std::vector<LinearDesc> &list, const std::string &suffix, char *text, int64_t capacity);
+
+#pragma GCC visibility pop
 
 // Debug tap table (tests only).
 struct DebugTaps {

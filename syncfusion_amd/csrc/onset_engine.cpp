@@ -147,36 +147,16 @@ struct OnsetExec {
       SF_HIP(launch_conv_tw(o.dt, in, c.cin_ld, c.cin_real, c.wtw, c.w.bias, res, c.cout_ld, out, c.cout_ld, p.N, p.T, Ho * Wo, relu ? 1 : 0, s));
       return SF_ONSET_PATH_TW;
     }
-    ConvGemmArgs a;
-    a.geom = 1;
-    a.src = in;
-    a.src_ld = c.cin_ld;
-    a.w = c.w.w;
+    VConvGeom g;
+    g.cin = c.cin_real, g.cout = c.cout, g.T = p.T;
+    g.Hi = Hi, g.Wi = Wi, g.Ho = Ho, g.Wo = Wo;
+    g.kt = c.kt, g.kh = c.kh, g.kw = c.kw, g.sh = g.sw = c.sh, g.pt = c.pt, g.ph = g.pw = c.ph;
+    ConvGemmArgs a = vconv_args(g, p.N * p.T, in, c.cin_ld, c.w.w, c.w.K, out, c.cout_ld);
     a.bias = c.w.bias;
-    a.N = c.cout;
-    a.K = c.w.K;
-    a.cin = c.cin_ld;
-    a.taps = c.kt * c.kh * c.kw;
-    a.M = p.N * p.T * Ho * Wo;
-    a.To = a.Ti = p.T;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.Hi = Hi;
-    a.Wi = Wi;
-    a.kt = c.kt;
-    a.kh = c.kh;
-    a.kw = c.kw;
-    a.st = 1;
-    a.sh = a.sw = c.sh;
-    a.pt = c.pt;
-    a.ph = a.pw = c.ph;
-    a.out = out;
-    a.out_ld = c.cout_ld;
     a.n_store = c.cout_ld;
     a.res = res;
     a.res_ld = c.cout_ld;
     a.act = relu ? 1 : 0;
-    a.Lout = a.Lsrc = 1;
     // Column counts that neither 128- nor 192-wide macro tiles cover well (layer 2's 288 mid channels in 320-channel rows: 384 computed
     // columns either way, 25 % of the launch on padding): whole 192-wide tiles first, the remaining <= 128 columns as a second launch
     // (192 + 128 = 320 computed columns).  692 -> ~600 us per convolution at 32 clips.
@@ -203,17 +183,6 @@ struct OnsetExec {
 };
 
 }  // namespace
-
-#define SF_API_BEGIN try {
-#define SF_API_END                  \
-  }                                 \
-  catch (const EngineError &e) {    \
-    return e.code;                  \
-  }                                 \
-  catch (const std::exception &e) { \
-    set_error("%s", e.what());      \
-    return SF_ERR_INVALID;          \
-  }
 
 extern "C" {
 
@@ -320,37 +289,11 @@ int sf_onsetnet_forward(sf_onsetnet *h, const float *frames, int N, int T, int H
   }
   // AdaptiveAvgPool3d((None,1,1)) -> (N*T, 512); Linear(512,128)+ReLU; Linear(128,1)
   SF_HIP(launch_spatial_mean(h->dt, X, 512, N * T, hh * ww, 512, p.pooled, s));
-  {
-    ConvGemmArgs a;
-    a.src = p.pooled;
-    a.src_ld = 512;
-    a.w = h->fc0.w;
-    a.bias = h->fc0.bias;
-    a.N = 128;
-    a.K = 512;
-    a.cin = 512;
-    a.M = N * T;
-    a.out = p.hid;
-    a.out_ld = 128;
-    a.n_store = 128;
-    a.act = 1;
-    SF_HIP(launch_conv_gemm(F32, a, s));
-  }
-  {
-    ConvGemmArgs a;
-    a.src = p.hid;
-    a.src_ld = 128;
-    a.w = h->fc2.w;
-    a.bias = h->fc2.bias;
-    a.N = 1;
-    a.K = 128;
-    a.cin = 128;
-    a.M = N * T;
-    a.out = logits;
-    a.out_ld = 1;
-    a.n_store = 1;
-    SF_HIP(launch_conv_direct(F32, F32, a, s));
-  }
+  // both heads leave solo, Lout and Lsrc at their defaults (0, 1, 1), unlike the token engines' Linears
+  ConvGemmArgs fc0 = linear_args(p.pooled, N * T, 512, 128, h->fc0.w, h->fc0.bias, p.hid);
+  fc0.act = 1;
+  SF_HIP(launch_conv_gemm(F32, fc0, s));
+  SF_HIP(launch_conv_direct(F32, F32, linear_args(p.hid, N * T, 128, 1, h->fc2.w, h->fc2.bias, logits), s));
   return SF_OK;
   SF_API_END
 }

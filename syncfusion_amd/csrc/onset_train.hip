@@ -14,6 +14,7 @@
 //   spatial mean pool backward: a broadcast of dP / (H W)
 // No atomics: two identical passes give bit-identical results.
 #include "common.h"
+#include "gemm_args.h"
 #include "kernels.h"
 
 namespace sf {
@@ -501,34 +502,8 @@ hipError_t launch_vconv_pack_fwd(const float *w, const VConvGeom &g, int cin_ld,
 }
 
 hipError_t launch_vconv_fwd(const float *x, int cin_ld, const float *wpk, const VConvGeom &g, int64_t NT, float *y, int cout_ld, hipStream_t s) {
-  ConvGemmArgs a;
-  a.geom = 1;
-  a.src = x;
-  a.src_ld = cin_ld;
-  a.w = wpk;
-  a.N = g.cout;
-  a.K = vconv_k(g.taps(), cin_ld);
-  a.cin = cin_ld;
-  a.taps = g.taps();
-  a.M = (int)(NT * g.Ho * g.Wo);
-  a.To = a.Ti = g.T;
-  a.Ho = g.Ho;
-  a.Wo = g.Wo;
-  a.Hi = g.Hi;
-  a.Wi = g.Wi;
-  a.kt = g.kt;
-  a.kh = g.kh;
-  a.kw = g.kw;
-  a.st = 1;
-  a.sh = g.sh;
-  a.sw = g.sw;
-  a.pt = g.pt;
-  a.ph = g.ph;
-  a.pw = g.pw;
-  a.out = y;
-  a.out_ld = cout_ld;
+  ConvGemmArgs a = vconv_args(g, NT, x, cin_ld, wpk, vconv_k(g.taps(), cin_ld), y, cout_ld);
   a.n_store = cout_ld;
-  a.Lout = a.Lsrc = 1;
   a.solo = 1;
   return launch_conv_gemm(F32, a, s);
 }

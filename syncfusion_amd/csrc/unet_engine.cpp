@@ -1715,17 +1715,6 @@ void check_ws(const sf_unet *h, void *ws, int64_t ws_bytes, int B, int L0, bool 
 // ---------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------
-#define SF_API_BEGIN try {
-#define SF_API_END                 \
-  }                                \
-  catch (const EngineError &e) {   \
-    return e.code;                 \
-  }                                \
-  catch (const std::exception &e) {\
-    set_error("%s", e.what());     \
-    return SF_ERR_INVALID;         \
-  }
-
 extern "C" {
 
 int sf_unet_create(const sf_unet_config *cfg, const sf_tensor *weights, int n_weights, void *stream, sf_unet **out) {

@@ -12,17 +12,6 @@
 
 using namespace sf;
 
-#define SF_API_BEGIN try {
-#define SF_API_END                  \
-  }                                 \
-  catch (const EngineError &e) {    \
-    return e.code;                  \
-  }                                 \
-  catch (const std::exception &e) { \
-    set_error("%s", e.what());      \
-    return SF_ERR_INVALID;          \
-  }
-
 namespace {
 
 constexpr int IN_LD = 4;            // the examples' rows: one channel in 4 columns (sf_logmel_examples_forward)
@@ -164,8 +153,7 @@ int sf_vggish_forward(sf_vggish *h, const float *examples, int n, float *embeddi
   if (!h || !examples || !embeddings) fail(SF_ERR_INVALID, "null argument");
   if (n < 1) fail(SF_ERR_INVALID, "n must be at least 1");
   if (n > max_examples(h)) fail(SF_ERR_SHAPE, "at most %d examples per call", max_examples(h));
-  const int64_t need = ws_bytes_for(h, n);
-  if (!ws || ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  require_workspace(ws, ws_bytes, ws_bytes_for(h, n));
   hipStream_t s = static_cast<hipStream_t>(stream);
   Workspace wsp(ws, ws_bytes);
   float *buf[2] = {wsp.alloc_n<float>(n * h->max_row_floats), wsp.alloc_n<float>(n * h->max_row_floats)};
@@ -176,32 +164,16 @@ int sf_vggish_forward(sf_vggish *h, const float *examples, int n, float *embeddi
     float *dst = buf[flip];
     flip ^= 1;
     if (sg.cout) {
-      const VConvGeom g = geom_of(sg);
-      ConvGemmArgs a;
-      a.geom = 1;
-      a.src = cur;
-      a.src_ld = sg.cin_ld;
-      a.w = sg.w;
+      const VConvGeom g = geom_of(sg);   // T = 1: one example per "frame"
+      ConvGemmArgs a = vconv_args(g, n, cur, sg.cin_ld, sg.w, vconv_k(g.taps(), sg.cin_ld), dst, sg.cout_ld);
       a.bias = sg.bias;
-      a.N = sg.cout;
-      a.K = vconv_k(g.taps(), sg.cin_ld);
-      a.cin = sg.cin_ld;
-      a.taps = g.taps();
-      a.M = n * g.Ho * g.Wo;
-      a.To = a.Ti = 1;          // one example per "frame"
-      a.Ho = g.Ho, a.Wo = g.Wo, a.Hi = g.Hi, a.Wi = g.Wi;
-      a.kt = 1, a.kh = 3, a.kw = 3, a.st = a.sh = a.sw = 1, a.pt = 0, a.ph = a.pw = 1;
-      a.out = dst;
-      a.out_ld = sg.cout_ld;
       a.n_store = sg.cout_ld;   // columns cout .. cout_ld are written as zeros
       a.act = 1;
-      a.Lout = a.Lsrc = 1;
       a.solo = 1;
       SF_HIP(launch_conv_gemm(F32, a, s));
     } else {
       SF_HIP(launch_maxpool2x2_cl(cur, n, sg.Hi, sg.Wi, sg.cin_ld, dst, s));
-      if (pool_taps && pool_taps[pool])
-        SF_HIP(hipMemcpyAsync(pool_taps[pool], dst, (size_t)n * (sg.Hi / 2) * (sg.Wi / 2) * sg.cin_ld * 4, hipMemcpyDeviceToDevice, s));
+      copy_tap(pool_taps, pool, dst, (int64_t)n * (sg.Hi / 2) * (sg.Wi / 2) * sg.cin_ld, s);
       ++pool;
     }
     cur = dst;
@@ -212,22 +184,11 @@ int sf_vggish_forward(sf_vggish *h, const float *examples, int n, float *embeddi
     const bool last = i + 1 == h->fcs.size();
     float *dst = last ? embeddings : fbuf[flip];
     flip ^= 1;
-    ConvGemmArgs a;             // a 1x1 convolution on a 1x1 map: one row per example
-    a.geom = 1;
-    a.src = cur;
-    a.src_ld = f.cin;
-    a.w = f.w;
-    a.bias = f.bias;
-    a.N = f.n;
-    a.K = f.k;
-    a.cin = f.cin;
-    a.taps = 1;
-    a.M = n;
-    a.out = dst;
-    a.out_ld = f.n_ld;
-    a.n_store = f.n_ld;
+    ConvGemmArgs a = linear_args(cur, n, f.cin, f.n, f.w, f.bias, dst);
+    a.geom = 1;                 // a 1x1 convolution on a 1x1 map: one row per example
+    a.K = f.k;                  // the packed rows are padded to a multiple of 32
+    a.out_ld = a.n_store = f.n_ld;
     a.act = f.act;
-    a.Lout = a.Lsrc = 1;
     a.solo = 1;
     SF_HIP(launch_conv_gemm(F32, a, s));
     cur = dst;
