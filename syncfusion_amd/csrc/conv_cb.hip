@@ -12,7 +12,7 @@
 //                  (packed once per weight version: a wave's 16-byte-per-lane load is 1 KB contiguous), straight into registers,
 //                  all 24 loads of a wave issued up front behind the panel loads -- they do not depend on the producer kernel.
 //                  A workgroup streams 107-131 KB instead of 393 KB; d7 (M = 176): 192 workgroups x 115 KB = 22 MB.
-//                  Output: fp32 partial slabs  slab[cb][m][n]  (no bias), 16-byte stores.
+//                  Output: fp32 partial slabs  slab[cb][m][n]  (no bias), written through (sc1) in whole 128-byte lines.
 //   cb_reduce_gn   the launch that already followed conv1 (gn_silu) becomes the reducer: sum of the slabs + bias -> h (16-bit)
 //                  and the GroupNorm chunk partials of h; >= 176 workgroups instead of 32.  The second convolution applies
 //                  GroupNorm+SiLU from those partials in its panel prologue.
@@ -39,6 +39,38 @@ template <typename T> __device__ __forceinline__ Vec16<T> buf_ld16(__amdgpu_buff
   u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
   v.v = __builtin_bit_cast(decltype(v.v), raw);
   return v;
+}
+
+// Partial-slab stores of one wave's 32 x 32 fp32 tile: rows m0 .. m0 + 31 of the workgroup's own slab behind resource rB, col_b = byte offset of
+// the wave's first column; lane (fr, fh) holds v[g] = columns 8 g + 4 fh + 0..3 of row fr.  The NEXT launch reads the slabs on other XCDs, so
+// every byte has to leave this XCD's L2 before the kernel boundary.  sc1 (aux 16) writes it through while the kernel still runs instead of
+// leaving it to the write-back behind the kernel -- but a write-through store is one fabric write per contiguous piece, and in the
+// accumulator layout a store instruction touches 32 rows x 32 B.  So the tile passes through `stage` (SLAB_STAGE floats per wave: 16 rows at
+// a time, pitch 36 floats -- the 8 lanes of a row write 8 distinct 16-byte slots, a row is read back as 128 contiguous bytes) and every store
+// instruction writes 8 whole 128-byte lines (8 lanes x 16 B = one row), 4 instructions per tile as before.  Rows m >= M get the out-of-range
+// offset: the resource drops them.  Measured (profiles/HISTORY.md, "conv_cb slab stores"): whole lines + sc1 +1.4 .. 3.2 % on configs[1];
+// sc1 on the accumulator layout -3.5 %; whole lines with plain stores +0.5 .. 1.2 %.
+constexpr int SLAB_PITCH = 36, SLAB_STAGE = 16 * SLAB_PITCH;
+__device__ __forceinline__ void slab_store_tile(const __amdgpu_buffer_rsrc_t rB, float *const stage, const f32x4 (&v)[4], const int m0, const int M,
+                                                const unsigned row_b, const unsigned col_b, const int lane) {
+  const int fr = lane & 31, fh = lane >> 5, rr = lane >> 3, q = lane & 7;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    if ((fr >> 4) == h) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4 *>(stage + (fr & 15) * SLAB_PITCH + 8 * g + 4 * fh) = v[g];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the staging rows are the wave's own: LDS operations of a wave complete in order
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const f32x4 o = *reinterpret_cast<const f32x4 *>(stage + (8 * i + rr) * SLAB_PITCH + 4 * q);
+      const int m = m0 + 16 * h + 8 * i + rr;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rB, m < M ? (unsigned)m * row_b + col_b + 16u * q : OOB, 0, /*sc1*/ 16);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
 }
 
 // GroupNorm partials of one (clip, group) for the panel prologue are (mean, M2) pairs: pro 1, per statistics chunk of cb_reduce_gn
@@ -270,17 +302,17 @@ __global__ __launch_bounds__(256) void conv_cb_kernel(const void *const src, con
         }
   if constexpr (EPI == 0) {
   // ---- 7. partial slab ---------------------------------------------------------------------------------------------------------
-  float *sl = a.slab + (size_t)cb * M * N + nt * 128 + wave * 32 + 4 * fh;
+  // one resource per workgroup: its own slab (M * N * 4 < 2^31, conv_cb_shape_ok; the S slabs together need not fit 32 bits)
+  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(a.slab + (size_t)cb * M * N, 0, (unsigned)(M * N) * 4u, 0x00020000);
+  static_assert(4 * SLAB_STAGE * sizeof(float) <= PR * PITCHW * sizeof(T), "the four waves' staging rows fit the panel");
+  __syncthreads();   // every wave has read its last panel fragment
+  float *stage = reinterpret_cast<float *>(panel) + wave * SLAB_STAGE;
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
-    const int m = r0 + t * 32 + fr;
-    if (m < M) {
+    f32x4 v[4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 v = {acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
-        *reinterpret_cast<f32x4 *>(sl + (unsigned)(m * N + 8 * g)) = v;
-      }
-    }
+    for (int g = 0; g < 4; ++g) v[g] = f32x4{acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
+    slab_store_tile(rB, stage, v, r0 + t * 32, M, (unsigned)N * 4u, (unsigned)(nt * 128 + wave * 32) * 4u, lane);
   }
   } else if constexpr (EPI == 1) {
   // ---- 7a. direct_gn: h = acc + bias -> 16-bit; chunk statistics of the stored values.  M % 32 == 0: a tile is whole or absent.  The rounded
@@ -596,19 +628,18 @@ __global__ __launch_bounds__(256) void conv_cb_x3_kernel(const void *const src, 
         x3_mfma<X3_F16>(wh[tap * 8 + ks], wl[tap * 8 + ks], ah, al, acc[t], accL[t]);
       }
   // ---- 7. partial slab --------------------------------------------------------------------------------------------------------------------
-  float *sl = a.slab + (size_t)cb * M * N + nt * 128 + wave * 32 + 4 * fh;
+  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(a.slab + (size_t)cb * M * N, 0, (unsigned)(M * N) * 4u, 0x00020000);
+  static_assert(4 * SLAB_STAGE * sizeof(float) <= PR * PITCHW * sizeof(f16), "the four waves' staging rows fit the hi image");
+  __syncthreads();   // every wave has read its last panel fragment
+  float *stage = reinterpret_cast<float *>(panelH) + wave * SLAB_STAGE;
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
-    const int m = r0 + t * 32 + fr;
-    if (m < M) {
+    f32x4 v[4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 v;
+    for (int g = 0; g < 4; ++g)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaf(accL[t][4 * g + e], X3P<X3_F16>::INV, acc[t][4 * g + e]);
-        *reinterpret_cast<f32x4 *>(sl + (unsigned)(m * N + 8 * g)) = v;
-      }
-    }
+      for (int e = 0; e < 4; ++e) v[g][e] = fmaf(accL[t][4 * g + e], X3P<X3_F16>::INV, acc[t][4 * g + e]);
+    slab_store_tile(rB, stage, v, r0 + t * 32, M, (unsigned)N * 4u, (unsigned)(nt * 128 + wave * 32) * 4u, lane);
   }
 }
 

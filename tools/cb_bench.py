@@ -1,4 +1,4 @@
-"""Tuning aid (python tools/cb_bench.py): the channel-block split-K chain of conv_cb.hip against the launches it replaces, alone on
+"""Tuning aid (python tools/cb_bench.py [SF_CB_MT values, default 0,1,2,3,4]): the channel-block split-K chain of conv_cb.hip against the launches it replaces, alone on
 the chip, warm and HBM-cold weights, per U-Net depth at four clips per branch (configs[1]) and at larger batches.  One process per
 setting (the SF_CB_MT / SF_BENCH_COLD knobs are read once)."""
 import os
@@ -25,7 +25,7 @@ for name, B, L, Cc in shapes:
     print(f"  {name:8s} M={B*L:5d} C={Cc:4d}  cb: {cb}   | launch_conv_gemm auto: {old.value*1e3:.1f} us" if rc2 == 0 else f"  {name} cb: {cb}", flush=True)
 ''' % HERE
 for cold in ("0", "1"):
-    for mt in ("0", "1", "2", "3", "4"):
+    for mt in (sys.argv[1].split(",") if len(sys.argv) > 1 else ("0", "1", "2", "3", "4")):
         print(f"COLD={cold} SF_CB_MT={mt} (0 = automatic)", flush=True)
         env = dict(os.environ, SF_BENCH_COLD=cold, SF_CB_MT=mt)
         subprocess.run([sys.executable, "-c", CHILD], env=env, check=False)
