@@ -125,6 +125,15 @@ template <typename T> __device__ __forceinline__ Vec16<T> ld16(const T *p) {
   r.v = __builtin_bit_cast(decltype(r.v), raw);
   return r;
 }
+// 16 bytes through a wave-uniform buffer descriptor; a byte offset with the OOB bit set lies beyond every buffer (< 2 GiB) and the load
+// returns zeros without predication
+constexpr unsigned OOB = 0x80000000u;
+template <typename T> __device__ __forceinline__ Vec16<T> buf_ld16(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
+  Vec16<T> v;
+  u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
+  v.v = __builtin_bit_cast(decltype(v.v), raw);
+  return v;
+}
 template <typename T> __device__ __forceinline__ void st16(T *p, const Vec16<T> &x) {
   *reinterpret_cast<u32x4 *>(p) = __builtin_bit_cast(u32x4, x.v);
 }

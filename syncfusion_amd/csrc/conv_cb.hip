@@ -32,14 +32,6 @@ namespace {
 constexpr int KC = 128;         // input channels per workgroup (one K block = 3 taps x 128)
 constexpr int KC_LOG2 = 7;
 constexpr int NSLOT = 4;        // clips a (BM + 2 <= 130)-row panel may touch: L >= 44 (host guarantees it)
-constexpr unsigned OOB = 0x80000000u;
-
-template <typename T> __device__ __forceinline__ Vec16<T> buf_ld16(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-  Vec16<T> v;
-  u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-  v.v = __builtin_bit_cast(decltype(v.v), raw);
-  return v;
-}
 
 // Partial-slab stores of one wave's 32 x 32 fp32 tile: rows m0 .. m0 + 31 of the workgroup's own slab behind resource rB, col_b = byte offset of
 // the wave's first column; lane (fr, fh) holds v[g] = columns 8 g + 4 fh + 0..3 of row fr.  The NEXT launch reads the slabs on other XCDs, so

@@ -11,19 +11,13 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "gemm_args.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace sf {
 namespace {
 
-constexpr unsigned OOB = 0x80000000u;   // beyond every buffer: the load returns zero
-
-template <typename T> __device__ __forceinline__ Vec16<T> buf_ld16(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-  Vec16<T> v;
-  u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-  v.v = __builtin_bit_cast(decltype(v.v), raw);
-  return v;
-}
 
 // KW = K elements one wave multiplies per iteration (32 or 64); the workgroup stages BKT = 4*KW per iteration.
 // NSET = K chunks in flight per workgroup.  The weights of a denoising step stream from HBM (they do not fit the
@@ -59,15 +53,8 @@ __global__ __launch_bounds__(256) void conv_gemm_fast_kernel(const ConvGemmArgs 
     prefetch_slice(a.pf, (int)blockIdx.x - mtiles * ntiles, 256);
     return;
   }
-  int bid = blockIdx.x, mt, nt;
-  if (swz) {
-    const int xcd = bid & 7, j = bid >> 3;
-    nt = xcd + 8 * (j / mtiles);
-    mt = j % mtiles;
-  } else {
-    nt = bid / mtiles;
-    mt = bid % mtiles;
-  }
+  int mt, nt;
+  tile_of_block(blockIdx.x, mtiles, swz, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const int srow = tid / VPR, svec = tid % VPR;
 
@@ -224,69 +211,23 @@ __global__ __launch_bounds__(256) void conv_gemm_fast_kernel(const ConvGemmArgs 
 #pragma unroll
           for (int j = 0; j < TN; ++j) x3_mfma<X3 ? X3 : 1>(ah[i], al[i], bh[j], bl[j], acc[i][j], accL[i][j]);
       }
-    } else if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int s = 0; s < KW / 16; ++s) {
-        using frag = typename Frag16<T>::type;
-        frag af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const frag *>(As + (i * 32 + fr) * LD + kw0 + 16 * s + 8 * fh);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const frag *>(Bs + (j * 32 + fr) * LD + kw0 + 16 * s + 8 * fh);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma32x16(af[i], bfr[j], acc[i][j]);
-      }
     } else {
-#pragma unroll
-      for (int q = 0; q < KW / 8; ++q) {
-        f32x4 af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4 *>(As + (i * 32 + fr) * LD + kw0 + (KW / 2) * fh + 4 * q);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const f32x4 *>(Bs + (j * 32 + fr) * LD + kw0 + (KW / 2) * fh + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bfr[j][e], acc[i][j], 0, 0, 0);
-      }
+      mma_chunk<T, TM, TN, KW>(As, Bs, LD, kw0, fr, fh, acc);
     }
   };
 
   // ---- epilogue operands (bias, residual, per-clip scale / add): they depend on nothing the K loop computes, so with
   // one epilogue pass per thread (32x32 tiles) their loads are issued HERE and overlap the whole reduction instead of
   // costing a memory round trip after it ----------------------------------------------------------------------------
-  const T *res = static_cast<const T *>(a.res);
-  const bool has_res = res != nullptr, has_bs = a.bscale != nullptr, has_ba = a.badd != nullptr;
   constexpr int QN = BN / 4;
   constexpr int EIT = (BM * QN + 255) / 256;
-  constexpr bool HOIST = EIT == 1 && !LN;   // (the LN variant would pass 128 registers and lose a workgroup per CU)
-  struct EpiOps {
-    float bi[4], rv[4], sv[4], av[4], cu[4];
-  };
-  auto epi_load = [&](int it) {
-    EpiOps o;
-    const int idx = tid + it * 256;
-    const int ml = idx / QN, nq = idx - ml * QN;
-    const int m = m0 + ml, nb = n0 + nq * 4;
-    const int mc = min(m, a.M - 1);
-    const int b = (has_bs || has_ba) ? mc / a.Lout : 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int nc = min(nb + e, a.N - 1);
-      o.bi[e] = a.bias ? a.bias[nc] : 0.f;
-      o.rv[e] = has_res ? to_f(res[(size_t)mc * a.res_ld + nc]) : 0.f;
-      o.sv[e] = has_bs ? a.bscale[(size_t)b * a.bscale_ld + nc] : 1.f;
-      o.av[e] = has_ba ? a.badd[(size_t)b * a.badd_ld + nc] : 0.f;
-      o.cu[e] = ln_epi ? a.ln_colsum[nc] : 0.f;
-    }
-    return o;
+  constexpr bool HOIST = EIT == 1 && !LN;   // (the LN variant would pass 128 registers and lose a workgroup per CU; conv_gemm_wp hoists there too)
+  auto epi_ops = [&](int it) {
+    const int idx = tid + it * 256, ml = idx / QN, nq = idx - ml * QN;
+    return epi_load<T>(a, m0 + ml, n0 + nq * 4, ln_epi);
   };
   EpiOps eo0;
-  if constexpr (HOIST) eo0 = epi_load(0);
+  if constexpr (HOIST) eo0 = epi_ops(0);
 
 #pragma unroll
   for (int j = 0; j < NSET; ++j)
@@ -297,7 +238,7 @@ __global__ __launch_bounds__(256) void conv_gemm_fast_kernel(const ConvGemmArgs 
       const int r = tid >> 3, t8 = tid & 7;           // 8 threads per row, 32 rows
       const int m = min(m0 + r, a.M - 1);
       float mp[4], qp[4];
-      float sm = 0.f;
+      float sm = 0.f;   // summed in sequence (gemm_epilogue.h, ln_pool_row: the order is this kernel's own)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int pidx = t8 + 8 * j;
@@ -307,19 +248,10 @@ __global__ __launch_bounds__(256) void conv_gemm_fast_kernel(const ConvGemmArgs 
         qp[j] = pv.y;
         sm += pv.x;
       }
-      const float mean = sum8_dpp(sm) / (float)a.ln_nt;   // every partial covers 32 channels
-      float dq = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (t8 + 8 * j < a.ln_nt) {
-          const float d = mp[j] - mean;
-          dq += fmaf(32.f * d, d, qp[j]);
-        }
-      }
-      const float m2 = sum8_dpp(dq);
+      const float2 st = ln_pool_row(sm, mp, qp, t8, a.ln_nt, a.cin, a.ln_eps);
       if (t8 == 0) {
-        rowstat[2 * r] = mean;
-        rowstat[2 * r + 1] = rsqrtf(m2 / (float)a.cin + a.ln_eps);
+        rowstat[2 * r] = st.x;
+        rowstat[2 * r + 1] = st.y;
       }
     }
     if (a.ln_ss) {
@@ -355,19 +287,10 @@ __global__ __launch_bounds__(256) void conv_gemm_fast_kernel(const ConvGemmArgs 
   }
 
   // ---- cross-wave K reduction through LDS, row-major epilogue (operand loads batched, unconditional) ----
-  float *myred = red + (size_t)wave * BM * LDR;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if constexpr (X3) myred[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * LDR + j * 32 + fr] = fmaf(accL[i][j][r], X3P<X3 ? X3 : 1>::INV, acc[i][j][r]);
-        else myred[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * LDR + j * 32 + fr] = acc[i][j][r];
-      }
+  if constexpr (X3) acc_split_to_lds<LDR, X3>(red + (size_t)wave * BM * LDR, fr, fh, acc, accL);
+  else acc_to_lds<LDR>(red + (size_t)wave * BM * LDR, fr, fh, acc);
   __syncthreads();
 
-  T *out = static_cast<T *>(a.out);
 #pragma unroll
   for (int it = 0; it < EIT; ++it) {
     const int idx = tid + it * 256;
@@ -376,27 +299,15 @@ __global__ __launch_bounds__(256) void conv_gemm_fast_kernel(const ConvGemmArgs 
     const bool live = idx < BM * QN && m < a.M && nb < a.n_store;
     EpiOps eo;
     if constexpr (HOIST) eo = eo0;
-    else eo = epi_load(it);
-    const float *bi = eo.bi, *rv = eo.rv, *sv = eo.sv, *av = eo.av;
+    else eo = epi_ops(it);
+    const float *rv = eo.rv;
     const int mlc = min(ml, BM - 1);
-    f32x4 v = *reinterpret_cast<const f32x4 *>(red + (size_t)mlc * LDR + nq * 4);
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      f32x4 t = *reinterpret_cast<const f32x4 *>(red + ((size_t)w * BM + mlc) * LDR + nq * 4);
-      v[0] += t[0];
-      v[1] += t[1];
-      v[2] += t[2];
-      v[3] += t[3];
-    }
+    f32x4 v = sum4_partials<BM, LDR>(red, mlc, nq);
     float rvt[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) rvt[e] = rv[e];
     if constexpr (LN) {
-      if (ln_epi) {   // LayerNorm of the raw source folded into the accumulator
-        const float mu = rowstat[2 * mlc], rstd = rowstat[2 * mlc + 1];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = rstd * (v[e] - mu * eo.cu[e]);
-      }
+      if (ln_epi) ln_fold(v, rowstat[2 * mlc], rowstat[2 * mlc + 1], eo.cu);   // LayerNorm of the raw source folded into the accumulator
     }
     if constexpr (LN) {
       if (a.res_ln) {   // the residual is the LayerNorm-modulated source row itself
@@ -409,29 +320,13 @@ __global__ __launch_bounds__(256) void conv_gemm_fast_kernel(const ConvGemmArgs 
         for (int e = 0; e < 4; ++e) rvt[e] = fmaf((rv[e] - mu) * rstd, sc4[e], sh4[e]);
       }
     }
-    float xo[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n = nb + e;
-      float x = (v[e] + bi[e]) * sv[e] + rvt[e] + av[e];
-      x = n < a.N ? apply_act(x, a.act) : 0.f;
-      xo[e] = a.out_f32 ? x : to_f(from_f<T>(x));
-      if (live && n < a.n_store) {
-        if (a.out_f32) static_cast<float *>(a.out)[(size_t)m * a.out_ld + n] = x;
-        else out[(size_t)m * a.out_ld + n] = from_f<T>(x);
-      }
-    }
+    float x[4], xo[4];
+    epi_values<T>(a, v, eo.bi, eo.sv, rvt, eo.av, nb, x, xo);
+    epi_store<T>(a, m, nb, live, x);
     if constexpr (EIT == 1 && BN == 32) {
       if (a.rowpart_out) {   // (mean, M2) of this row's 32 stored values: 8 consecutive lanes hold them, 4 each
-        const float mean = sum8_dpp((xo[0] + xo[1]) + (xo[2] + xo[3])) * (1.0f / 32.0f);
-        float q = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = xo[e] - mean;
-          q = fmaf(d, d, q);
-        }
-        q = sum8_dpp(q);
-        if (nq == 0 && live) *reinterpret_cast<float2 *>(a.rowpart_out + ((size_t)m * a.rowpart_nt + nt) * 2) = make_float2(mean, q);
+        const float2 st = row32_stats(xo);
+        if (nq == 0 && live) *reinterpret_cast<float2 *>(a.rowpart_out + ((size_t)m * a.rowpart_nt + nt) * 2) = st;
       }
     }
   }
@@ -444,12 +339,7 @@ template <typename T, int BM, int BN, bool CAT, int KW, int NSET, bool LN = fals
   constexpr size_t red_bytes = (size_t)4 * BM * (BN + 4) * sizeof(float);
   size_t lds = stage_bytes > red_bytes ? stage_bytes : red_bytes;
   if (LN) lds = (lds + 15) / 16 * 16 + (size_t)(2 * BM + (a.ln_ss ? 4 * a.cin : 0)) * sizeof(float);   // rowstat (+ modulation table)
-  const int mtiles = (a.M + BM - 1) / BM, ntiles = (a.n_store + BN - 1) / BN;
-  const int swz = (ntiles % 8 == 0) ? 1 : 0;
-  const size_t es = sizeof(T);
-  const size_t bA = (size_t)(a.M / a.Lout + (a.M % a.Lout ? 1 : 0)) * a.Lsrc * a.src_ld * es;
-  const size_t bA2 = CAT ? (size_t)a.M * a.src2_ld * es : 0;
-  const size_t bW = (size_t)a.N * a.K * es;
+  const GemmTiling t = gemm_tiling(a, BM, BN, sizeof(T), CAT);
   auto kern = conv_gemm_fast_kernel<T, BM, BN, CAT, KW, NSET, LN, X3>;
   static bool en = false;
   if (!en) {
@@ -457,7 +347,7 @@ template <typename T, int BM, int BN, bool CAT, int KW, int NSET, bool LN = fals
     if (e != hipSuccess) return e;
     en = true;
   }
-  hipLaunchKernelGGL(kern, dim3(mtiles * ntiles + (a.pf.ptr && a.pf.bytes >= 16 ? a.pf.wgs : 0)), dim3(256), lds, s, a, mtiles, ntiles, swz, (unsigned)bA, (unsigned)bA2, (unsigned)bW);
+  hipLaunchKernelGGL(kern, dim3(t.grid), dim3(256), lds, s, a, t.mtiles, t.ntiles, t.swz, t.bytesA, t.bytesA2, t.bytesW);
   return hipGetLastError();
 }
 
@@ -493,13 +383,7 @@ template <typename T> hipError_t launch_fast(const ConvGemmArgs &a, const ConvGe
 bool conv_gemm_fast_ok(int dt, const ConvGemmArgs &a) {
   if (a.geom != 0 || a.pro != 0 || a.taps > 3 || a.taps < 1) return false;
   if ((a.cin % 128) || (a.cin2 % 32) || (a.K % 32)) return false;
-  const size_t es = dsize(dt);
-  const size_t lim = 0x7FFFFFF0ull;
-  const size_t clips = (size_t)(a.M / a.Lout + 1);
-  if (clips * a.Lsrc * a.src_ld * es >= lim) return false;
-  if ((size_t)a.M * (a.src2_ld > 0 ? a.src2_ld : 1) * es >= lim) return false;
-  if ((size_t)a.N * a.K * es >= lim) return false;
-  return true;
+  return gemm_buffers_below_2g(dt, a);
 }
 
 hipError_t launch_conv_gemm_fast(int dt, const ConvGemmArgs &a, const ConvGemmPlan &p, hipStream_t s) { return SF_DISPATCH_T(dt, launch_fast<T>(a, p, s)); }

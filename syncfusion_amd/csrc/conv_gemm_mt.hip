@@ -34,7 +34,6 @@ namespace {
 
 constexpr int BK = 64;                 // K step of the 16-bit types: 64 elements = 128 bytes = 8 sixteen-byte chunks per row
 constexpr int ROWB = 128;              // bytes per staged row (fp32: 32 elements per K step)
-constexpr unsigned OOB = 0x80000000u;
 constexpr int NSTAGE = 3;
 
 typedef __attribute__((address_space(3))) void lds_void;

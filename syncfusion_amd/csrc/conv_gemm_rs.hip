@@ -17,12 +17,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_args.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace sf {
 namespace {
 
-constexpr unsigned OOB = 0x80000000u;
 constexpr int LDR = 36;   // row pitch of a partial tile in LDS (floats)
 
 // T1: one tap (1x1 / Linear), a compile-time switch so that the two address schemes do not meet at a join
@@ -208,99 +209,38 @@ __global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const void *const wim
   // ---- the four partial tiles meet here (fixed order: deterministic) ------------------------------------------------------------
   float *rowstat = red + 4 * 32 * LDR, *gsum = rowstat + 64;
   if (ln_epi) {
-    const float mean = sum8_dpp((ln_mp[0] + ln_mp[1]) + (ln_mp[2] + ln_mp[3])) / (float)a.ln_nt;   // every partial covers 32 channels
-    float dq = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (nq + 8 * j < a.ln_nt) {
-        const float d = ln_mp[j] - mean;
-        dq += fmaf(32.f * d, d, ln_qp[j]);
-      }
-    const float m2 = sum8_dpp(dq);
+    const float2 st = ln_pool_row((ln_mp[0] + ln_mp[1]) + (ln_mp[2] + ln_mp[3]), ln_mp, ln_qp, nq, a.ln_nt, a.cin, a.ln_eps);
     if (nq == 0) {
-      rowstat[2 * ml] = mean;
-      rowstat[2 * ml + 1] = rsqrtf(m2 / (float)a.cin + a.ln_eps);
+      rowstat[2 * ml] = st.x;
+      rowstat[2 * ml + 1] = st.y;
     }
   }
+  // (gemm_epilogue.h's acc32_to_lds, written out: through the shared function the split forms allocate 2-4 registers more)
   float *myred = red + wave * 32 * LDR;
 #pragma unroll
   for (int r = 0; r < 16; ++r) myred[((r & 3) + 8 * (r >> 2) + 4 * fh) * LDR + fr] = acc[r];
   __syncthreads();
 
   const bool live = em < a.M && enb < a.n_store;
-  f32x4 v = *reinterpret_cast<const f32x4 *>(red + ml * LDR + nq * 4);
+  f32x4 v = sum4_partials<32, LDR>(red, ml, nq);
+  if (ln_epi) ln_fold(v, rowstat[2 * ml], rowstat[2 * ml + 1], cu);
+  float x[4], xo[4];
+  epi_values<T>(a, v, bi, sv, rv, av, enb, x, xo);
+  if (a.out_f32) epi_store<T>(a, em, enb, live, x);
+  else if (live) {   // whole quads leave as one 8-byte store
+    T ob[4];
 #pragma unroll
-  for (int w = 1; w < 4; ++w) {
-    const f32x4 t = *reinterpret_cast<const f32x4 *>(red + (w * 32 + ml) * LDR + nq * 4);
-    v += t;
-  }
-  if (ln_epi) {
-    const float mu = rowstat[2 * ml], rstd = rowstat[2 * ml + 1];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = rstd * (v[e] - mu * cu[e]);
-  }
-  float xo[4];
-  T ob[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int n = enb + e;
-    float x = (v[e] + bi[e]) * sv[e] + rv[e] + av[e];
-    x = n < a.N ? apply_act(x, a.act) : 0.f;
-    ob[e] = from_f<T>(x);
-    xo[e] = a.out_f32 ? x : to_f(ob[e]);
-    if (live && n < a.n_store && a.out_f32) static_cast<float *>(a.out)[(size_t)em * a.out_ld + n] = x;
-  }
-  if (live && !a.out_f32) {
+    for (int e = 0; e < 4; ++e) ob[e] = from_f<T>(x[e]);
     T *op = static_cast<T *>(a.out) + (size_t)em * a.out_ld + enb;
     if (enb + 3 < a.n_store && (a.out_ld & 3) == 0) __builtin_memcpy(__builtin_assume_aligned(op, 4 * sizeof(T)), ob, 4 * sizeof(T));
     else
       for (int e = 0; e < 4; ++e)
         if (enb + e < a.n_store) op[e] = ob[e];
   }
-  if (a.rowpart_out) {   // row-LayerNorm partial of the stored values (ConvGemmArgs, conv_gemm_fast.hip)
-    const float mean = sum8_dpp((xo[0] + xo[1]) + (xo[2] + xo[3])) * (1.0f / 32.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d = xo[e] - mean;
-      q = fmaf(d, d, q);
-    }
-    q = sum8_dpp(q);
-    if (nq == 0 && live) *reinterpret_cast<float2 *>(a.rowpart_out + ((size_t)em * a.rowpart_nt + nt) * 2) = make_float2(mean, q);
-  }
-  if (a.gnpart_out) {   // GroupNorm tile statistics of the stored values for the channel-block convolution that follows (kernels.h)
-    const float mean = sum8_dpp((xo[0] + xo[1]) + (xo[2] + xo[3])) * (1.0f / 32.0f);   // (mean, M2) of the row's 32 stored values
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d = xo[e] - mean;
-      q = fmaf(d, d, q);
-    }
-    q = sum8_dpp(q);
-    if (nq == 0) {
-      gsum[2 * ml] = mean;
-      gsum[2 * ml + 1] = q;
-    }
-    __syncthreads();
-    if (tid < 2) {   // segment 0: rows of the first row's clip; segment 1: rows of the next clip
-      const int rbnd = min((m0 / a.Lout + 1) * a.Lout - m0, 32);
-      const int lo = tid == 0 ? 0 : rbnd, hi = tid == 0 ? rbnd : min(32, a.M - m0);   // rows past M belong to no clip
-      // the segment's (mean, M2) from its rows' (32 values each, row order), in one pass about the first row's mean p:
-      // d_r = mean_r - p,  mean = p + sum d / k,  M2 = sum (M2_r + 32 d_r^2) - 32 (sum d)^2 / k.  (0, 0) when empty
-      const float p = hi > lo ? gsum[2 * lo] : 0.f;
-      float t1 = 0.f, t2 = 0.f;
-      for (int r = lo; r < hi; ++r) {
-        const float d = gsum[2 * r] - p;
-        t1 += d;
-        t2 += fmaf(32.f * d, d, gsum[2 * r + 1]);
-      }
-      const float dk = hi > lo ? t1 / (float)(hi - lo) : 0.f;
-      t2 = fmaxf(fmaf(-32.f * t1, dk, t2), 0.f);
-      t1 = p + dk;
-      // (n_store + 31) >> 5 is the head's `ntiles` again, by launch_rs_head's formula (the head's registers are free by now): whoever
-      // changes the column tiling there changes it here
-      *reinterpret_cast<float2 *>(a.gnpart_out + (((size_t)mt * ((a.n_store + 31) >> 5) + nt) * 2 + tid) * 2) = make_float2(t1, t2);
-    }
+  if (a.rowpart_out || a.gnpart_out) {   // statistics of the stored values (kernels.h: rowpart_out, gnpart_out)
+    const float2 st = row32_stats(xo);
+    if (a.rowpart_out && nq == 0 && live) *reinterpret_cast<float2 *>(a.rowpart_out + ((size_t)em * a.rowpart_nt + nt) * 2) = st;
+    if (a.gnpart_out) gn_tile_stats(a, gsum, st, tid, ml, nq, m0, mt, nt, ntiles);
   }
 }
 
@@ -339,17 +279,11 @@ bool rs_geo_fits(const ConvGemmArgs &a) {
 
 template <typename Kern> hipError_t launch_rs_head(Kern kern, const ConvGemmArgs &a, const void *wimg, size_t es, bool cat, hipStream_t s) {
   if (!rs_geo_fits(a)) return hipErrorInvalidValue;
-  const int mtiles = (a.M + 31) / 32, ntiles = (a.n_store + 31) / 32;
-  const int swz = (ntiles % 8 == 0) ? 1 : 0;
-  const size_t bA = (size_t)(a.M / a.Lout + (a.M % a.Lout ? 1 : 0)) * a.Lsrc * a.src_ld * es;
-  const size_t bA2 = cat ? (size_t)a.M * a.src2_ld * es : 0;
-  const size_t bW = (size_t)a.N * a.K * es;
-  const dim3 grid(mtiles * ntiles + (a.pf.ptr && a.pf.bytes >= 16 ? a.pf.wgs : 0));
+  const GemmTiling t = gemm_tiling(a, 32, 32, es, cat);
   const unsigned geo = (unsigned)a.taps | ((unsigned)a.stride << 8) | ((unsigned)a.pad << 12) | ((unsigned)a.up_shift << 20) | ((unsigned)(a.cin >> 4) << 24);
   const void *const src = a.src;
-  const unsigned bytesW = (unsigned)bW, bytesA = (unsigned)bA, bytesA2 = (unsigned)bA2;
-  const int ntiles_swz = (ntiles << 1) | swz, K = a.K, M = a.M, Lout = a.Lout, Lsrc = a.Lsrc, src_ld = a.src_ld;
-  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, wimg, src, bytesW, bytesA, mtiles, ntiles_swz, K, M, Lout, Lsrc, src_ld, geo, a, bytesA2);
+  const int ntiles_swz = (t.ntiles << 1) | t.swz, K = a.K, M = a.M, Lout = a.Lout, Lsrc = a.Lsrc, src_ld = a.src_ld;
+  hipLaunchKernelGGL(kern, dim3(t.grid), dim3(256), 0, s, wimg, src, t.bytesW, t.bytesA, t.mtiles, ntiles_swz, K, M, Lout, Lsrc, src_ld, geo, a, t.bytesA2);
   return hipGetLastError();
 }
 
@@ -384,7 +318,6 @@ template <typename T, bool CAT> hipError_t launch_rs(const ConvGemmArgs &a, hipS
 bool conv_gemm_rs_ok(int dt, const ConvGemmArgs &a) {
   static const bool off = tune_env("SF_NO_RS") != nullptr;   // A/B aid
   const bool x3 = dt == F32 && a.wfrx != nullptr && a.wx_mode == X3_F16;   // the split-operand form (fp32 activations)
-  const size_t es = x3 ? 4 : 2;
   if (off || (dt == F32 && !x3) || (!x3 && !a.wfr) || a.geom != 0 || a.pro != 0 || a.taps < 1) return false;
   if (!rs_geo_fits(a)) return false;   // the argument head's packed geometry (stride <= 15, pad <= 255, up_shift <= 15)
   if ((a.K % 64) || a.K > (x3 ? 1280 : 2048) || (a.cin % 16) || (a.cin2 % 16) || (a.N % 32) || a.n_store != a.N) return false;
@@ -392,11 +325,7 @@ bool conv_gemm_rs_ok(int dt, const ConvGemmArgs &a) {
   if ((a.res && (a.res_ld % 4)) || (a.bscale && (a.bscale_ld % 4)) || (a.badd && (a.badd_ld % 4)) || (a.out_ld % 4)) return false;   // vector epilogue loads
   if (a.ln_ss || a.res_ln) return false;   // the operand-side LayerNorm (Modulation folded into InjectChannels) stays on conv_gemm_fast
   if (a.ln_colsum && (!a.ln_part || a.ln_nt * 32 != a.cin || a.ln_nt > 32 || a.cin2)) return false;
-  const size_t lim = 0x7FFFFFF0ull;
-  if ((size_t)(a.M / a.Lout + 1) * a.Lsrc * a.src_ld * es >= lim) return false;
-  if ((size_t)a.M * (a.src2_ld > 0 ? a.src2_ld : 1) * es >= lim) return false;
-  if ((size_t)a.N * a.K * es >= lim) return false;
-  return true;
+  return gemm_buffers_below_2g(dt, a);   // (dt == F32 is the split form here: 4-byte activations)
 }
 
 hipError_t launch_pack_wfrx(const float *w, int N, int K, void *out, hipStream_t s) {

@@ -11,6 +11,8 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "gemm_args.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace sf {
@@ -46,15 +48,8 @@ __global__ __launch_bounds__(256) void conv_gemm_sk_kernel(const ConvGemmArgs a,
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // ---- block -> (row tile, column tile); keep one W panel's row tiles on one XCD ---------------------
-  int bid = blockIdx.x, mt, nt;
-  if (swz) {  // ntiles % 8 == 0: XCD x (= bid % 8 under round-robin dispatch) owns column tiles == x (mod 8)
-    const int xcd = bid & 7, j = bid >> 3;
-    nt = xcd + 8 * (j / mtiles);
-    mt = j % mtiles;
-  } else {
-    nt = bid / mtiles;
-    mt = bid % mtiles;
-  }
+  int mt, nt;
+  tile_of_block(blockIdx.x, mtiles, swz, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
 
   const T *src = static_cast<const T *>(a.src);
@@ -212,38 +207,7 @@ __global__ __launch_bounds__(256) void conv_gemm_sk_kernel(const ConvGemmArgs a,
   const int fr = lane & 31, fh = lane >> 5;
   const int kw0 = 32 * wave;  // this wave's sub-slice of the chunk
 
-  auto compute = [&]() {
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        using frag = typename Frag16<T>::type;
-        frag af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const frag *>(As + (i * 32 + fr) * LD + kw0 + 16 * s + 8 * fh);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const frag *>(Bs + (j * 32 + fr) * LD + kw0 + 16 * s + 8 * fh);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma32x16(af[i], bfr[j], acc[i][j]);
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f32x4 af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4 *>(As + (i * 32 + fr) * LD + kw0 + 16 * fh + 4 * q);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const f32x4 *>(Bs + (j * 32 + fr) * LD + kw0 + 16 * fh + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bfr[j][e], acc[i][j], 0, 0, 0);
-      }
-    }
-  };
+  auto compute = [&]() { mma_chunk<T, TM, TN, 32>(As, Bs, LD, kw0, fr, fh, acc); };
 
   prefetch(0, s0);
   if (nkt > 1) prefetch(1, s1);
@@ -263,18 +227,9 @@ __global__ __launch_bounds__(256) void conv_gemm_sk_kernel(const ConvGemmArgs a,
   }
 
   // ---- cross-wave K reduction through LDS, then a row-major epilogue -------------------------------
-  float *myred = red + (size_t)wave * BM * LDR;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) myred[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * LDR + j * 32 + fr] = acc[i][j][r];
+  acc_to_lds<LDR>(red + (size_t)wave * BM * LDR, fr, fh, acc);
   __syncthreads();
 
-  T *out = static_cast<T *>(a.out);
-  const T *res = static_cast<const T *>(a.res);
-  const bool has_res = res != nullptr, has_bs = a.bscale != nullptr, has_ba = a.badd != nullptr;
   constexpr int QN = BN / 4;
 #pragma unroll
   for (int it = 0; it < (BM * QN + 255) / 256; ++it) {
@@ -282,38 +237,11 @@ __global__ __launch_bounds__(256) void conv_gemm_sk_kernel(const ConvGemmArgs a,
     const int ml = idx / QN, nq = idx - ml * QN;
     const int m = m0 + ml, nb = n0 + nq * 4;
     const bool live = idx < BM * QN && m < a.M && nb < a.n_store;
-    const int mc = min(m, a.M - 1);
-    // operands first (unconditional, clamped): all loads of this row segment are in flight together
-    float bi[4], rv[4], sv[4], av[4];
-    const int b = (has_bs || has_ba) ? mc / a.Lout : 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int nc = min(nb + e, a.N - 1);
-      bi[e] = a.bias ? a.bias[nc] : 0.f;
-      rv[e] = has_res ? to_f(res[(size_t)mc * a.res_ld + nc]) : 0.f;
-      sv[e] = has_bs ? a.bscale[(size_t)b * a.bscale_ld + nc] : 1.f;
-      av[e] = has_ba ? a.badd[(size_t)b * a.badd_ld + nc] : 0.f;
-    }
-    const int mlc = min(ml, BM - 1);
-    f32x4 v = *reinterpret_cast<const f32x4 *>(red + (size_t)mlc * LDR + nq * 4);
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      f32x4 t = *reinterpret_cast<const f32x4 *>(red + ((size_t)w * BM + mlc) * LDR + nq * 4);
-      v[0] += t[0];
-      v[1] += t[1];
-      v[2] += t[2];
-      v[3] += t[3];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n = nb + e;
-      float x = (v[e] + bi[e]) * sv[e] + rv[e] + av[e];
-      x = n < a.N ? apply_act(x, a.act) : 0.f;
-      if (live && n < a.n_store) {
-        if (a.out_f32) static_cast<float *>(a.out)[(size_t)m * a.out_ld + n] = x;
-        else out[(size_t)m * a.out_ld + n] = from_f<T>(x);
-      }
-    }
+    const EpiOps eo = epi_load<T>(a, m, nb, false);   // operands first: all loads of this row segment are in flight together
+    const f32x4 v = sum4_partials<BM, LDR>(red, min(ml, BM - 1), nq);
+    float x[4], xo[4];
+    epi_values<T>(a, v, eo.bi, eo.sv, eo.rv, eo.av, nb, x, xo);
+    epi_store<T>(a, m, nb, live, x);
   }
 }
 
@@ -326,8 +254,7 @@ template <typename T, int BM, int BN, int GEOM, bool CAT, bool PRO> hipError_t l
     int nb = min(a.M / a.Lout + (a.M % a.Lout ? 1 : 0), BM / a.Lout + 2);
     lds += (size_t)nb * (a.cin + a.G) * sizeof(float2);
   }
-  const int mtiles = (a.M + BM - 1) / BM, ntiles = (a.n_store + BN - 1) / BN;
-  const int swz = (ntiles % 8 == 0) ? 1 : 0;
+  const GemmTiling t = gemm_tiling(a, BM, BN, sizeof(T), CAT);
   auto kern = conv_gemm_sk_kernel<T, BM, BN, GEOM, CAT, PRO>;
   static bool en = false;
   if (!en) {
@@ -335,7 +262,7 @@ template <typename T, int BM, int BN, int GEOM, bool CAT, bool PRO> hipError_t l
     if (e != hipSuccess) return e;
     en = true;
   }
-  hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, s, a, mtiles, ntiles, swz);
+  hipLaunchKernelGGL(kern, dim3(t.tiles()), dim3(256), lds, s, a, t.mtiles, t.ntiles, t.swz);   // (hosts no prefetch workgroups)
   return hipGetLastError();
 }
 

@@ -11,20 +11,13 @@
 //   * epilogue through LDS: row-major 16-byte stores, operand loads (bias / residual / per-clip scale+add)
 //     batched and unconditional.
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace sf {
 namespace {
 
 constexpr int BK = 64;
-constexpr unsigned OOB = 0x80000000u;
-
-template <typename T> __device__ __forceinline__ Vec16<T> buf_ld16(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-  Vec16<T> v;
-  u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-  v.v = __builtin_bit_cast(decltype(v.v), raw);
-  return v;
-}
 
 struct V2Extra {
   int mtiles, ntiles, swz;
@@ -53,17 +46,7 @@ __global__ __launch_bounds__(256) void conv_gemm_v2_kernel(const ConvGemmArgs a,
   const int wr = wave >> 1, wc = wave & 1;
   // ---- block -> (row tile, column tile): all users of one W panel on one XCD ----------------------------
   int mt, nt;
-  {
-    const int bid = blockIdx.x;
-    if (x.swz) {
-      const int xcd = bid & 7, j = bid >> 3;
-      mt = j % x.mtiles;
-      nt = xcd + 8 * (j / x.mtiles);
-    } else {
-      mt = bid % x.mtiles;
-      nt = bid / x.mtiles;
-    }
-  }
+  tile_of_block(blockIdx.x, x.mtiles, x.swz, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const int srow = tid / VPR, svec = tid % VPR;
 
@@ -204,37 +187,7 @@ __global__ __launch_bounds__(256) void conv_gemm_v2_kernel(const ConvGemmArgs a,
   const int fr = lane & 31, fh = lane >> 5;
   auto compute = [&](int buf) {
     const T *As = lds + buf * STAGE + (wr * WTM) * LD, *Bs = lds + buf * STAGE + (BM + wc * WTN) * LD;
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int s = 0; s < BK / 16; ++s) {
-        using frag = typename Frag16<T>::type;
-        frag af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const frag *>(As + (i * 32 + fr) * LD + 16 * s + 8 * fh);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const frag *>(Bs + (j * 32 + fr) * LD + 16 * s + 8 * fh);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma32x16(af[i], bfr[j], acc[i][j]);
-      }
-    } else {
-      // fp32: v_mfma_f32_32x32x2_f32; the two k of a step are {s, 32 + s} of the chunk (same permutation for A and W)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        f32x4 af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4 *>(As + (i * 32 + fr) * LD + 32 * fh + 4 * q);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const f32x4 *>(Bs + (j * 32 + fr) * LD + 32 * fh + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bfr[j][e], acc[i][j], 0, 0, 0);
-      }
-    }
+    mma_chunk<T, TM, TN, BK>(As, Bs, LD, 0, fr, fh, acc);
   };
 
   // ---- K loop: loads of chunk t+1 in flight under the MFMAs of chunk t; one barrier per chunk ---------------
@@ -272,48 +225,22 @@ __global__ __launch_bounds__(256) void conv_gemm_v2_kernel(const ConvGemmArgs a,
   }
 
   // ---- accumulators -> LDS (fp32, row-major) --------------------------------------------------------------
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        red[(wr * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * LDR + wc * WTN + j * 32 + fr] = acc[i][j][r];
+  acc_to_lds<LDR>(red + (wr * WTM) * LDR + wc * WTN, fr, fh, acc);
   __syncthreads();
 
   constexpr int QN = BN / 4;
   constexpr int ITER = (BM * QN) / 256;
-  T *out = static_cast<T *>(a.out);
-  const T *res = static_cast<const T *>(a.res);
-  const bool has_res = res != nullptr, has_bs = a.bscale != nullptr, has_ba = a.badd != nullptr;
 #pragma unroll
   for (int it = 0; it < ITER; ++it) {
     const int idx = tid + it * 256;
     const int ml = idx / QN, nq = idx - ml * QN;
     const int m = m0 + ml, nb = n0 + nq * 4;
     const bool live = m < a.M && nb < a.n_store;
-    const int mc = min(m, a.M - 1);
-    float bi[4], rv[4], sv[4], av[4];
-    const int b = (has_bs || has_ba) ? mc / a.Lout : 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int nc = min(nb + e, a.N - 1);
-      bi[e] = a.bias ? a.bias[nc] : 0.f;
-      rv[e] = has_res ? to_f(res[(size_t)mc * a.res_ld + nc]) : 0.f;
-      sv[e] = has_bs ? a.bscale[(size_t)b * a.bscale_ld + nc] : 1.f;
-      av[e] = has_ba ? a.badd[(size_t)b * a.badd_ld + nc] : 0.f;
-    }
-    const f32x4 v = *reinterpret_cast<const f32x4 *>(red + (size_t)ml * LDR + nq * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n = nb + e;
-      float xv = (v[e] + bi[e]) * sv[e] + rv[e] + av[e];
-      xv = n < a.N ? apply_act(xv, a.act) : 0.f;
-      if (live && n < a.n_store) {
-        if (a.out_f32) static_cast<float *>(a.out)[(size_t)m * a.out_ld + n] = xv;
-        else out[(size_t)m * a.out_ld + n] = from_f<T>(xv);
-      }
-    }
+    const EpiOps eo = epi_load<T>(a, m, nb, false);
+    const f32x4 v = *reinterpret_cast<const f32x4 *>(red + (size_t)ml * LDR + nq * 4);   // one tile: nothing to sum
+    float xv[4], xo[4];
+    epi_values<T>(a, v, eo.bi, eo.sv, eo.rv, eo.av, nb, xv, xo);
+    epi_store<T>(a, m, nb, live, xv);
   }
 }
 

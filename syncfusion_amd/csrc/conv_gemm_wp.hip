@@ -14,20 +14,14 @@
 //     execute in order: only lgkmcnt waits, no s_barrier);
 //   * the four partial tiles meet once, in the epilogue (fixed-order sum through LDS -> deterministic).
 #include "common.h"
+#include "gemm_args.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace sf {
 namespace {
 
 constexpr int BK = 64;
-constexpr unsigned OOB = 0x80000000u;
-
-template <typename T> __device__ __forceinline__ Vec16<T> buf_ld16(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-  Vec16<T> v;
-  u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-  v.v = __builtin_bit_cast(decltype(v.v), raw);
-  return v;
-}
 
 // NSET = K chunks a wave keeps in flight (register sets); ONE private LDS staging buffer per wave suffices because a
 // wave's LDS operations execute in program order (the next chunk's writes queue behind this chunk's fragment reads).
@@ -55,15 +49,8 @@ __global__ __launch_bounds__(256) void conv_gemm_wp_kernel(const ConvGemmArgs a,
     prefetch_slice(a.pf, (int)blockIdx.x - mtiles * ntiles, 256);
     return;
   }
-  int bid = blockIdx.x, mt, nt;
-  if (swz) {
-    const int xcd = bid & 7, j = bid >> 3;
-    nt = xcd + 8 * (j / mtiles);
-    mt = j % mtiles;
-  } else {
-    nt = bid / mtiles;
-    mt = bid % mtiles;
-  }
+  int mt, nt;
+  tile_of_block(blockIdx.x, mtiles, swz, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
   const int lrow = lane / VPR, lvec = lane % VPR;
 
@@ -199,71 +186,26 @@ __global__ __launch_bounds__(256) void conv_gemm_wp_kernel(const ConvGemmArgs a,
 #pragma unroll
           for (int j = 0; j < TN; ++j) x3_mfma<X3 ? X3 : 1>(ah[i], al[i], bh[j], bl[j], acc[i][j], accL[i][j]);
       }
-    } else if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int s = 0; s < BK / 16; ++s) {
-        using frag = typename Frag16<T>::type;
-        frag af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const frag *>(As + (i * 32 + fr) * LD + 16 * s + 8 * fh);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const frag *>(Bs + (j * 32 + fr) * LD + 16 * s + 8 * fh);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma32x16(af[i], bfr[j], acc[i][j]);
-      }
     } else {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        f32x4 af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4 *>(As + (i * 32 + fr) * LD + 32 * fh + 4 * q);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const f32x4 *>(Bs + (j * 32 + fr) * LD + 32 * fh + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bfr[j][e], acc[i][j], 0, 0, 0);
-      }
+      mma_chunk<T, TM, TN, BK>(As, Bs, LD, 0, fr, fh, acc);
     }
   };
 
-  // ---- epilogue operands: loaded up front when one epilogue pass per thread suffices (see conv_gemm_fast.hip) ------
-  const T *res = static_cast<const T *>(a.res);
-  const bool has_res = res != nullptr, has_bs = a.bscale != nullptr, has_ba = a.badd != nullptr;
+  // ---- epilogue operands: loaded up front when one epilogue pass per thread suffices (they depend on nothing the K loop computes, so
+  // their loads overlap the whole reduction instead of costing a memory round trip after it) ------------------------------------------
   constexpr int QN = BN / 4;
   constexpr int EIT = (BM * QN + 255) / 256;
-  constexpr bool HOIST = EIT == 1;
-  // LayerNorm of the raw source folded into the accumulator (the qkv projection behind the attention pre-norm, see
-  // conv_gemm_fast.hip): out = rstd_m * (acc - mean_m * colsum(W)_n); the row statistics are pooled from the producer's per-tile
-  // partials, whose loads ride with the epilogue operands in front of the K loop (32-row tiles only)
+  constexpr bool HOIST = EIT == 1;   // (with the accumulator-side LayerNorm too: conv_gemm_fast's LN variant does not hoist)
+  // LayerNorm of the raw source folded into the accumulator (the qkv projection behind the attention pre-norm; gemm_epilogue.h): the row
+  // statistics are pooled from the producer's per-tile partials, whose loads ride with the epilogue operands in front of the K loop
+  // (32-row tiles only)
   const bool ln_epi = BM == 32 && a.ln_colsum != nullptr;
-  struct EpiOps {
-    float bi[4], rv[4], sv[4], av[4], cu[4];
-  };
-  auto epi_load = [&](int it) {
-    EpiOps o;
-    const int idx = tid + it * 256;
-    const int ml = idx / QN, nq = idx - ml * QN;
-    const int m = m0 + ml, nb = n0 + nq * 4;
-    const int mc = min(m, a.M - 1);
-    const int b = (has_bs || has_ba) ? mc / a.Lout : 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int nc = min(nb + e, a.N - 1);
-      o.bi[e] = a.bias ? a.bias[nc] : 0.f;
-      o.rv[e] = has_res ? to_f(res[(size_t)mc * a.res_ld + nc]) : 0.f;
-      o.sv[e] = has_bs ? a.bscale[(size_t)b * a.bscale_ld + nc] : 1.f;
-      o.av[e] = has_ba ? a.badd[(size_t)b * a.badd_ld + nc] : 0.f;
-      o.cu[e] = ln_epi ? a.ln_colsum[nc] : 0.f;
-    }
-    return o;
+  auto epi_ops = [&](int it) {
+    const int idx = tid + it * 256, ml = idx / QN, nq = idx - ml * QN;
+    return epi_load<T>(a, m0 + ml, n0 + nq * 4, ln_epi);
   };
   EpiOps eo0;
-  if constexpr (HOIST) eo0 = epi_load(0);
+  if constexpr (HOIST) eo0 = epi_ops(0);
   float ln_mp[4] = {0.f, 0.f, 0.f, 0.f}, ln_qp[4] = {0.f, 0.f, 0.f, 0.f};
   if (ln_epi) {   // 8 threads per row: partial t8 + 8 j of row tid >> 3
     const int m = min(m0 + (tid >> 3), a.M - 1), t8 = tid & 7;
@@ -303,34 +245,16 @@ __global__ __launch_bounds__(256) void conv_gemm_wp_kernel(const ConvGemmArgs a,
   float *rowstat = red + (size_t)4 * BM * LDR;   // (mean, rstd) per row, behind the four partial tiles
   float *gsum = rowstat + 2 * BM;                // (mean, M2) per row of the stored tile (gnpart_out)
   if (ln_epi) {
-    const int t8 = tid & 7;
-    const float mean = sum8_dpp((ln_mp[0] + ln_mp[1]) + (ln_mp[2] + ln_mp[3])) / (float)a.ln_nt;   // every partial covers 32 channels
-    float dq = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (t8 + 8 * j < a.ln_nt) {
-        const float d = ln_mp[j] - mean;
-        dq += fmaf(32.f * d, d, ln_qp[j]);
-      }
-    const float m2 = sum8_dpp(dq);
-    if (t8 == 0) {
-      rowstat[2 * (tid >> 3)] = mean;
-      rowstat[2 * (tid >> 3) + 1] = rsqrtf(m2 / (float)a.cin + a.ln_eps);
+    const float2 st = ln_pool_row((ln_mp[0] + ln_mp[1]) + (ln_mp[2] + ln_mp[3]), ln_mp, ln_qp, tid & 7, a.ln_nt, a.cin, a.ln_eps);
+    if ((tid & 7) == 0) {
+      rowstat[2 * (tid >> 3)] = st.x;
+      rowstat[2 * (tid >> 3) + 1] = st.y;
     }
   }
-  float *myred = red + (size_t)wave * BM * LDR;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if constexpr (X3) myred[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * LDR + j * 32 + fr] = fmaf(accL[i][j][r], X3P<X3 ? X3 : 1>::INV, acc[i][j][r]);
-        else myred[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * LDR + j * 32 + fr] = acc[i][j][r];
-      }
+  if constexpr (X3) acc_split_to_lds<LDR, X3>(red + (size_t)wave * BM * LDR, fr, fh, acc, accL);
+  else acc_to_lds<LDR>(red + (size_t)wave * BM * LDR, fr, fh, acc);
   __syncthreads();
 
-  T *out = static_cast<T *>(a.out);
 #pragma unroll
   for (int it = 0; it < EIT; ++it) {
     const int idx = tid + it * 256;
@@ -339,78 +263,18 @@ __global__ __launch_bounds__(256) void conv_gemm_wp_kernel(const ConvGemmArgs a,
     const bool live = idx < BM * QN && m < a.M && nb < a.n_store;
     EpiOps eo;
     if constexpr (HOIST) eo = eo0;
-    else eo = epi_load(it);
-    const float *bi = eo.bi, *rv = eo.rv, *sv = eo.sv, *av = eo.av;
+    else eo = epi_ops(it);
     const int mlc = min(ml, BM - 1);
-    f32x4 v = *reinterpret_cast<const f32x4 *>(red + (size_t)mlc * LDR + nq * 4);
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      f32x4 t = *reinterpret_cast<const f32x4 *>(red + ((size_t)w * BM + mlc) * LDR + nq * 4);
-      v[0] += t[0];
-      v[1] += t[1];
-      v[2] += t[2];
-      v[3] += t[3];
-    }
-    if (ln_epi) {
-      const float mu = rowstat[2 * mlc], rstd = rowstat[2 * mlc + 1];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = rstd * (v[e] - mu * eo.cu[e]);
-    }
-    float xo[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n = nb + e;
-      float x = (v[e] + bi[e]) * sv[e] + rv[e] + av[e];
-      x = n < a.N ? apply_act(x, a.act) : 0.f;
-      xo[e] = a.out_f32 ? x : to_f(from_f<T>(x));
-      if (live && n < a.n_store) {
-        if (a.out_f32) static_cast<float *>(a.out)[(size_t)m * a.out_ld + n] = x;
-        else out[(size_t)m * a.out_ld + n] = from_f<T>(x);
-      }
-    }
+    f32x4 v = sum4_partials<BM, LDR>(red, mlc, nq);
+    if (ln_epi) ln_fold(v, rowstat[2 * mlc], rowstat[2 * mlc + 1], eo.cu);
+    float x[4], xo[4];
+    epi_values<T>(a, v, eo.bi, eo.sv, eo.rv, eo.av, nb, x, xo);
+    epi_store<T>(a, m, nb, live, x);
     if constexpr (HOIST && BN == 32) {
-      if (a.rowpart_out) {   // row-LayerNorm partial of the stored values (see ConvGemmArgs, conv_gemm_fast.hip)
-        const float mean = sum8_dpp((xo[0] + xo[1]) + (xo[2] + xo[3])) * (1.0f / 32.0f);
-        float q = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = xo[e] - mean;
-          q = fmaf(d, d, q);
-        }
-        q = sum8_dpp(q);
-        if (nq == 0 && live) *reinterpret_cast<float2 *>(a.rowpart_out + ((size_t)m * a.rowpart_nt + nt) * 2) = make_float2(mean, q);
-      }
-      if (a.gnpart_out) {   // GroupNorm tile statistics of the stored values for the channel-block convolution that follows (kernels.h)
-        const float mean = sum8_dpp((xo[0] + xo[1]) + (xo[2] + xo[3])) * (1.0f / 32.0f);   // (mean, M2) of the row's 32 stored values
-        float q = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = xo[e] - mean;
-          q = fmaf(d, d, q);
-        }
-        q = sum8_dpp(q);
-        if (nq == 0) {
-          gsum[2 * ml] = mean;
-          gsum[2 * ml + 1] = q;
-        }
-        __syncthreads();
-        if (tid < 2) {   // segment 0: rows of the first row's clip; segment 1: rows of the next clip.  Fixed order: deterministic
-          const int rb = min((m0 / a.Lout + 1) * a.Lout - m0, BM);
-          const int lo = tid == 0 ? 0 : rb, hi = tid == 0 ? rb : min(BM, a.M - m0);   // rows past M belong to no clip
-          // the segment's (mean, M2) from its rows' (32 values each, row order), in one pass about the first row's mean p:
-          // d_r = mean_r - p,  mean = p + sum d / k,  M2 = sum (M2_r + 32 d_r^2) - 32 (sum d)^2 / k.  (0, 0) when empty
-          const float p = hi > lo ? gsum[2 * lo] : 0.f;
-          float t1 = 0.f, t2 = 0.f;
-          for (int r = lo; r < hi; ++r) {
-            const float d = gsum[2 * r] - p;
-            t1 += d;
-            t2 += fmaf(32.f * d, d, gsum[2 * r + 1]);
-          }
-          const float dk = hi > lo ? t1 / (float)(hi - lo) : 0.f;
-          t2 = fmaxf(fmaf(-32.f * t1, dk, t2), 0.f);
-          t1 = p + dk;
-          *reinterpret_cast<float2 *>(a.gnpart_out + (((size_t)mt * ntiles + nt) * 2 + tid) * 2) = make_float2(t1, t2);
-        }
+      if (a.rowpart_out || a.gnpart_out) {   // statistics of the stored values (kernels.h: rowpart_out, gnpart_out)
+        const float2 st = row32_stats(xo);
+        if (a.rowpart_out && nq == 0 && live) *reinterpret_cast<float2 *>(a.rowpart_out + ((size_t)m * a.rowpart_nt + nt) * 2) = st;
+        if (a.gnpart_out) gn_tile_stats(a, gsum, st, tid, ml, nq, m0, mt, nt, ntiles);
       }
     }
   }
@@ -422,12 +286,7 @@ template <typename T, int BM, int BN, bool CAT, int NSET, int X3 = 0> hipError_t
   constexpr size_t red_bytes = (size_t)4 * BM * (BN + 4) * sizeof(float) + (size_t)4 * BM * sizeof(float);   // + (mean, rstd) and (sum, sumsq) per row
   const size_t lds = stage_bytes > red_bytes ? stage_bytes : red_bytes;
   if (lds > 150 * 1024) return hipErrorInvalidValue;   // fp32 64-row tiles do not fit: the caller falls back
-  const int mtiles = (a.M + BM - 1) / BM, ntiles = (a.n_store + BN - 1) / BN;
-  const int swz = (ntiles % 8 == 0) ? 1 : 0;
-  const size_t es = sizeof(T);
-  const size_t bA = (size_t)(a.M / a.Lout + (a.M % a.Lout ? 1 : 0)) * a.Lsrc * a.src_ld * es;
-  const size_t bA2 = CAT ? (size_t)a.M * a.src2_ld * es : 0;
-  const size_t bW = (size_t)a.N * a.K * es;
+  const GemmTiling t = gemm_tiling(a, BM, BN, sizeof(T), CAT);
   auto kern = conv_gemm_wp_kernel<T, BM, BN, CAT, NSET, X3>;
   static bool en = false;
   if (!en) {
@@ -435,7 +294,7 @@ template <typename T, int BM, int BN, bool CAT, int NSET, int X3 = 0> hipError_t
     if (e != hipSuccess) return e;
     en = true;
   }
-  hipLaunchKernelGGL(kern, dim3(mtiles * ntiles + (a.pf.ptr && a.pf.bytes >= 16 ? a.pf.wgs : 0)), dim3(256), lds, s, a, mtiles, ntiles, swz, (unsigned)bA, (unsigned)bA2, (unsigned)bW);
+  hipLaunchKernelGGL(kern, dim3(t.grid), dim3(256), lds, s, a, t.mtiles, t.ntiles, t.swz, t.bytesA, t.bytesA2, t.bytesW);
   return hipGetLastError();
 }
 
@@ -461,11 +320,7 @@ template <typename T> hipError_t launch_wp(const ConvGemmArgs &a, int tile, int 
 bool conv_gemm_wp_ok(int dt, const ConvGemmArgs &a) {
   if (a.geom != 0 || a.pro != 0 || a.taps < 1) return false;
   if ((a.cin % BK) || (a.cin2 % 32) || (a.K % 32)) return false;
-  const size_t es = dsize(dt), lim = 0x7FFFFFF0ull;
-  if ((size_t)(a.M / a.Lout + 1) * a.Lsrc * a.src_ld * es >= lim) return false;
-  if ((size_t)a.M * (a.src2_ld > 0 ? a.src2_ld : 1) * es >= lim) return false;
-  if ((size_t)a.N * a.K * es >= lim) return false;
-  return true;
+  return gemm_buffers_below_2g(dt, a);
 }
 
 hipError_t launch_conv_gemm_wp(int dt, const ConvGemmArgs &a, int tile, int split, hipStream_t s) { return SF_DISPATCH_T(dt, launch_wp<T>(a, tile, split, s)); }

@@ -61,5 +61,34 @@ inline ConvGemmArgs vconv_args(const VConvGeom &g, int64_t NT, const void *src, 
   return a;
 }
 
+// The launch geometry the wave-split-K kernels share (conv_gemm_sk / _fast / _wp / _rs, 1-D rows): BM x BN tiles over M x n_store, the XCD
+// swizzle of the block -> tile map (gemm_epilogue.h, tile_of_block), the byte lengths of the three buffer descriptors (es = bytes per
+// element, cat = a second source is read) and the grid with the hosted prefetch workgroups behind the tiles (kernels.h, Prefetch; a kernel
+// that hosts none launches tiles() workgroups).
+struct GemmTiling {
+  int mtiles, ntiles, swz;
+  unsigned bytesA, bytesA2, bytesW, grid;
+  unsigned tiles() const { return (unsigned)(mtiles * ntiles); }
+};
+inline GemmTiling gemm_tiling(const ConvGemmArgs &a, int BM, int BN, size_t es, bool cat) {
+  GemmTiling t;
+  t.mtiles = (a.M + BM - 1) / BM;
+  t.ntiles = (a.n_store + BN - 1) / BN;
+  t.swz = (t.ntiles % 8 == 0) ? 1 : 0;
+  t.bytesA = (unsigned)((size_t)(a.M / a.Lout + (a.M % a.Lout ? 1 : 0)) * a.Lsrc * a.src_ld * es);
+  t.bytesA2 = cat ? (unsigned)((size_t)a.M * a.src2_ld * es) : 0u;
+  t.bytesW = (unsigned)((size_t)a.N * a.K * es);
+  t.grid = t.tiles() + (a.pf.ptr && a.pf.bytes >= 16 ? a.pf.wgs : 0);
+  return t;
+}
+// every buffer a 1-D launch reads through a 32-bit descriptor offset stays below 2 GiB (the OOB bit of common.h lies beyond it)
+inline bool gemm_buffers_below_2g(int dt, const ConvGemmArgs &a) {
+  const size_t es = dsize(dt), lim = 0x7FFFFFF0ull;
+  if ((size_t)(a.M / a.Lout + 1) * a.Lsrc * a.src_ld * es >= lim) return false;
+  if ((size_t)a.M * (a.src2_ld > 0 ? a.src2_ld : 1) * es >= lim) return false;
+  if ((size_t)a.N * a.K * es >= lim) return false;
+  return true;
+}
+
 #pragma GCC visibility pop
 }  // namespace sf

@@ -103,20 +103,23 @@ struct ConvGemmArgs {
   // caller's hint: a short reduction (128 <= K < 256) on short activations still takes the small-batch 32x32 family instead of the classic
   // 64x64 tile -- the InjectChannels GEMM (K = 160) behind the direct channel-block chain: 352 workgroups instead of 88
   int short_k = 0;
-  // Row-LayerNorm fusion (conv_gemm_fast / conv_gemm_wp, 32x32 tiles only):
+  // Row-LayerNorm fusion (conv_gemm_fast / conv_gemm_wp / conv_gemm_rs, 32x32 tiles only):
   //   producer side: rowpart_out != nullptr -> the epilogue also writes, per output row and 32-column tile, the (mean, M2)
-  //     of the STORED values: rowpart_out[(m * rowpart_nt + n_tile) * 2 + {0,1}]   (rowpart_nt = n_store / 32);
+  //     of the STORED values: rowpart_out[(m * rowpart_nt + n_tile) * 2 + {0,1}]   (rowpart_nt = n_store / 32); the bits are
+  //     gemm_epilogue.h's row32_stats, the one text every producer calls;
   //   consumer side (launch_conv_gemm_ln): the first source (cin channels, one tap) is read as
   //     LayerNorm_cin(src; ln_eps) * (1 + ln_ss[b][c]) + ln_ss[b][cin + c]  (ln_ss == nullptr: plain normalisation), the row
   //     statistics pooled from ln_part (ln_nt = cin / 32 partials per row); res_ln: the residual rows get the same transform.
   float *rowpart_out = nullptr;
   int rowpart_nt = 0;
-  // GroupNorm partials of the STORED output for the channel-block convolution that consumes it (conv_gemm_wp, 32x32 tiles, 1-D,
-  // Lout >= 32 so that a tile touches at most two clips): gnpart_out[((m_tile * (n_store / 32) + n_tile) * 2 + seg) * 2 + {0,1}] =
+  // GroupNorm partials of the STORED output for the channel-block convolution that consumes it (conv_gemm_wp / conv_gemm_rs, 32x32 tiles,
+  // 1-D, Lout >= 32 so that a tile touches at most two clips): gnpart_out[((m_tile * (n_store / 32) + n_tile) * 2 + seg) * 2 + {0,1}] =
   // (mean, M2) over the tile's rows of the clip of its first row (seg 0) and of the next clip (seg 1); (0, 0) for an empty segment.
+  // Written by gemm_epilogue.h's gn_tile_stats (from row32_stats), which defines the bits.
   float *gnpart_out = nullptr;
   //     ln_colsum != nullptr (plain normalisation, no second source): the source is multiplied RAW and the LayerNorm is
-  //     applied to the accumulator instead,  rstd_m * (acc[m][n] - mean_m * ln_colsum[n]),  ln_colsum[n] = sum_k w[n][k].
+  //     applied to the accumulator instead,  rstd_m * (acc[m][n] - mean_m * ln_colsum[n]),  ln_colsum[n] = sum_k w[n][k]
+  //     (gemm_epilogue.h: ln_pool_row pools the row statistics, ln_fold applies them).
   const float *ln_colsum = nullptr;
   const float *ln_part = nullptr, *ln_ss = nullptr;
   int ln_nt = 0, ln_ss_ld = 0, res_ln = 0;

@@ -10,7 +10,16 @@ the two metadata values `.amdhsa_user_sgpr_count` and `.amdhsa_user_sgpr_kernarg
 
 The kernarg segment pointer takes two of the 16 user SGPRs, so at most 14 dwords are preloaded; the compiler preloads LEADING scalar and
 pointer parameters only and stops at the first by-value struct (syncfusion_amd/csrc/Makefile).  The tool reads these
-two metadata lines and nothing else of the assembly."""
+two metadata lines and nothing else of the assembly.
+
+    python tools/kernarg_preload_report.py --resources conv_gemm_sk.hip [...]
+
+prints instead, from the same `.amdhsa_` block and the compiler's comments behind it, what a refactor of a kernel must not move:
+
+    <file> <TAB> next_free_vgpr <TAB> accum_offset <TAB> next_free_sgpr <TAB> private_segment_fixed_size (scratch) <TAB>
+    group_segment_fixed_size (static LDS) <TAB> occupancy (waves per SIMD) <TAB> code bytes <TAB> <demangled kernel name>
+
+Compare two trees with `diff` on the two outputs (profiles/gemm_epilogue_resources.txt)."""
 import os
 import re
 import shutil
@@ -46,20 +55,30 @@ def demangle(names):
     return out if len(out) == len(names) else list(names)
 
 
-def report(source):
-    """[(kernel name, user SGPR count, preload length)] of one .hip source, in the order of the assembly."""
+RES_KEYS = ("next_free_vgpr", "accum_offset", "next_free_sgpr", "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def report(source, resources=False):
+    """[(kernel name, user SGPR count, preload length)] of one .hip source, in the order of the assembly; resources: [(kernel name, the five
+    RES_KEYS values, occupancy, code bytes)]."""
     hipcc, flags = makefile_vars()
     path = source if os.path.exists(source) else os.path.join(CSRC, source)
     with tempfile.TemporaryDirectory() as tmp:
         asm = os.path.join(tmp, "device.s")
         subprocess.run([hipcc] + flags + ["-I", CSRC, "--cuda-device-only", "-S", path, "-o", asm], check=True, cwd=tmp)
-        rows, cur = [], None
+        rows, cur, res, last = [], None, {}, None
         for line in open(asm):
             w = line.split()
             if not w:
                 continue
+            if w[0] == ";" and len(w) >= 3 and w[1] in ("Occupancy:", "codeLenInByte") and last:   # the compiler's summary behind the kernel's .amdhsa_ block
+                res[last][w[1].rstrip(":")] = int(w[-1])
+            elif cur is not None and w[0].startswith(".amdhsa_") and w[0][8:] in RES_KEYS:
+                res[cur[0]][w[0][8:]] = int(w[1])
             if w[0] == ".amdhsa_kernel":
                 cur = [w[1], 0, 0]
+                res[w[1]] = {}
+                last = w[1]
             elif cur is not None and w[0] == ".amdhsa_user_sgpr_count":
                 cur[1] = int(w[1])
             elif cur is not None and w[0] == ".amdhsa_user_sgpr_kernarg_preload_length":
@@ -68,6 +87,8 @@ def report(source):
                 rows.append(cur)
                 cur = None
     names = demangle([r[0] for r in rows])
+    if resources:
+        return [(n,) + tuple(res[r[0]].get(k, -1) for k in RES_KEYS + ("Occupancy", "codeLenInByte")) for n, r in zip(names, rows)]
     return [(n, r[1], r[2]) for n, r in zip(names, rows)]
 
 
@@ -75,9 +96,10 @@ def main(argv):
     if not argv:
         print(__doc__)
         return 2
-    for src in argv:
-        for name, user, pre in report(src):
-            print(f"{os.path.basename(src)}\t{user}\t{pre}\t{name}", flush=True)
+    resources = argv[0] == "--resources"
+    for src in argv[resources:]:
+        for row in report(src, resources):
+            print("\t".join([os.path.basename(src)] + [str(v) for v in row[1:]] + [row[0]]), flush=True)
     return 0
 
 
