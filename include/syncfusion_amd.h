@@ -464,6 +464,51 @@ int64_t sf_op_inject_prenorm_proj_workspace_bytes(int B, int L, int C, int C2, i
 int sf_op_inject_prenorm_proj(int dtype, const void *m, const void *ctx, const float *w_inj, const float *b_inj, const float *gamma,
                               const float *beta, float eps, const float *w_q, int B, int L, int C, int C2, int N, void *z_out, void *q_out,
                               int *fused_out, void *ws, int64_t ws_bytes, void *stream);
+/* ONE implicit-GEMM launch with the whole epilogue of the small-batch kernels exposed, for element-wise tests of the epilogue operands and
+ * of the statistics a launch leaves for the next one (tests/gemm_epilogue_ref.py; no reference counterpart).  Channels-last rows:
+ *   out = act((conv(nearest_up(x)) | x2 . w + bias) * bscale[b] + residual + badd[b])        Lout = (L * upsample + 2 pad - taps) / stride + 1
+ * x (B, L, C) and x2 (B, Lout, C2; optional, taps == 1) and residual (B, Lout, N) in `dtype`; w is the GEMM's own matrix (N, taps * C + C2)
+ * in fp32, column tap * C + c for the first source and taps * C + c2 for the second, 16-byte aligned; bias (N), bscale and badd (B, N) fp32;
+ * act 0 none, 1 relu, 2 gelu(erf), 3 silu(gelu); out (B, Lout, N) in `dtype`, or fp32 when out_f32.  C, C2 multiples of 32.
+ * Optional outputs, written only where the dispatcher's plan for these arguments honours them (the *_done flags say so; a declined one is
+ * left untouched):  rowpart (B * Lout, N / 32, 2) = (mean, M2) of each row's 32 STORED values per column tile;  gnpart
+ * (ceil(B * Lout / 32), N / 32, 2, 2) = (mean, M2) of the stored values of each 32 x 32 tile over its rows of the first row's clip
+ * (segment 0) and of the next clip (segment 1); an empty segment is (0, 0).
+ * The LayerNorm-consumer launch (sf_op_conv1d_ln, taps == 1): the first source is read as LayerNorm_C(x; ln_eps), its row statistics pooled
+ * from ln_part (B * L, C / 32, 2) in rowpart's layout.  ln_operand == 0: accumulator side -- the raw rows are multiplied and the epilogue
+ * applies rstd * (acc - mean * colsum(w)), the column sums taken of the packed weight as the engine takes them.  ln_operand == 1: the operand
+ * is transformed, LayerNorm(x) * (1 + ln_ss[b][c]) + ln_ss[b][C + c] with ln_ss (B, 2 C) fp32 or NULL; res_ln: the residual (N == C) gets
+ * the same transform.  mt_ln offers the macro-tile form of both fusions; solo says that nothing runs beside the launch.
+ * Both launches size their workspace with sf_op_conv1d_epi_workspace_bytes.  Every entry refuses with SF_ERR_UNSUPPORTED before anything is
+ * launched (the weight images are packed behind the plan) where no kernel takes the arguments.  The _variant queries need
+ * no device and take no data pointers' contents: only whether an optional pointer is set enters the plan; they return the label of the
+ * kernel and the flags from the same finished launch arguments as the real call. */
+typedef struct {
+  int32_t dtype, B, L, C, C2, N, taps, stride, pad, upsample, act, out_f32, mt_ln, res_ln, ln_operand, solo;
+  float ln_eps;
+  int32_t reserved;
+  const void *x, *x2;
+  const float *w, *bias, *bscale, *badd;
+  const void *residual;
+  void *out;
+  float *rowpart, *gnpart;
+  const float *ln_part, *ln_ss;
+} sf_conv1d_epi_desc;
+int64_t sf_op_conv1d_epi_workspace_bytes(const sf_conv1d_epi_desc *d);
+int sf_op_conv1d_epi(const sf_conv1d_epi_desc *d, int *rowpart_done, int *gnpart_done, void *ws, int64_t ws_bytes, void *stream);
+int sf_op_conv1d_epi_variant(const sf_conv1d_epi_desc *d, char *label, int label_bytes, int *rowpart_done, int *gnpart_done);
+int sf_op_conv1d_ln(const sf_conv1d_epi_desc *d, int *rowpart_done, void *ws, int64_t ws_bytes, void *stream);
+int sf_op_conv1d_ln_variant(const sf_conv1d_epi_desc *d, char *label, int label_bytes, int *rowpart_done);
+/* The channel-block convolution behind the TILE statistics a producing GEMM leaves (conv_cb prologue 2, then cb_reduce_gn), bf16 / fp16 /
+ * fp32x:   h = Conv1d_k3(SiLU(GroupNorm(x; groups, gn_g, gn_b, eps))) + bias        x, h: (B, L, C) channels-last in `dtype`, w (C, C, 3) fp32.
+ * tile_stats is read in gnpart's layout, (ceil(B * L / 32), C / 32, 2, 2) fp32: (mean, M2) of x per 32-row x 32-column tile and clip segment.
+ * stats_out (B, nch, groups, 2) receives the reducer's chunk statistics of the stored h ((mean, M2) per chunk of chunk_rows rows; the two
+ * counts are returned, nch <= 32).  SF_ERR_UNSUPPORTED before anything is launched where the convolution or its prologue does not take the
+ * shape (C a power-of-two multiple of 128 up to 1024, L >= 44, C / groups a power of two >= 32, at most 32 tiles per clip and group). */
+int64_t sf_op_conv_cb_tiles_workspace_bytes(int dtype, int B, int L, int C);
+int sf_op_conv_cb_tiles(int dtype, const void *x, const float *w, const float *bias, const float *gn_g, const float *gn_b, int groups, float eps,
+                        const float *tile_stats, int B, int L, int C, void *h_out, float *stats_out, int *nch_out, int *chunk_rows_out, void *ws,
+                        int64_t ws_bytes, void *stream);
 /* Kernel tuning aid: average milliseconds of the four launches of that chain on random data (ms[0] convolution, ms[1] reduction +
  * GroupNorm sums, ms[2] convolution with prologue, ms[3] reduction + LayerNorm); cold != 0 streams the weights from HBM. */
 int sf_bench_conv_cb(int dtype, int B, int L, int C, int groups, int kb, int cold, int iters, float *ms /* [4] */);

@@ -53,6 +53,14 @@ class VConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "T", "Hi", "Wi", "cin", "cin_ld", "cout", "cout_ld", "kt", "kh", "kw", "sh", "sw", "pt", "ph", "pw")]
 
 
+class Conv1dEpiDesc(C.Structure):
+    """sf_conv1d_epi_desc: one implicit-GEMM launch with its whole epilogue (sf_op_conv1d_epi / sf_op_conv1d_ln)."""
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "B", "L", "C", "C2", "N", "taps", "stride", "pad", "upsample", "act", "out_f32", "mt_ln", "res_ln",
+                                         "ln_operand", "solo")] + \
+               [("ln_eps", C.c_float), ("reserved", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("x", "x2", "w", "bias", "bscale", "badd", "residual", "out", "rowpart", "gnpart", "ln_part", "ln_ss")]
+
+
 SF_CLAP_MAX_STAGES = 8
 
 
@@ -157,6 +165,15 @@ SYMBOLS = {
     "sf_op_gn_silu": (_I, [_I, _P, _P, _P, _I, _F, _I, _I, _I, _P, _P, _L, _P]),
     "sf_op_inject_prenorm_proj_workspace_bytes": (_L, [_I, _I, _I, _I, _I]),
     "sf_op_inject_prenorm_proj": (_I, [_I, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    # one launch with the whole epilogue: (desc, rowpart_done, gnpart_done, ws, ws_bytes, stream); the queries (desc, label, label_bytes, flags...)
+    "sf_op_conv1d_epi_workspace_bytes": (_L, [C.POINTER(Conv1dEpiDesc)]),
+    "sf_op_conv1d_epi": (_I, [C.POINTER(Conv1dEpiDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), _P, _L, _P]),
+    "sf_op_conv1d_epi_variant": (_I, [C.POINTER(Conv1dEpiDesc), C.c_char_p, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sf_op_conv1d_ln": (_I, [C.POINTER(Conv1dEpiDesc), C.POINTER(C.c_int), _P, _L, _P]),
+    "sf_op_conv1d_ln_variant": (_I, [C.POINTER(Conv1dEpiDesc), C.c_char_p, _I, C.POINTER(C.c_int)]),
+    # (dtype, x, w, bias, gn_g, gn_b, groups, eps, tile_stats, B, L, C, h_out, stats_out, nch_out, chunk_rows_out, ws, ws_bytes, stream)
+    "sf_op_conv_cb_tiles_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "sf_op_conv_cb_tiles": (_I, [_I, _P, _P, _P, _P, _P, _I, _F, _P, _I, _I, _I, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, _L, _P]),
     "sf_op_resnet_mod_cb_workspace_bytes": (_L, [_I, _I, _I]),
     "sf_op_resnet_mod_cb": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _F, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
     "sf_op_resnet_mod_cbd_workspace_bytes": (_L, [_I, _I, _I, _I]),

@@ -838,6 +838,247 @@ int sf_op_inject_prenorm_proj(int dtype, const void *m, const void *ctx, const f
   SF_API_END
 }
 
+// ---- sf_op_conv1d_epi / sf_op_conv1d_ln: one launch with the whole epilogue exposed (tests/gemm_epilogue_ref.py) --------------------------
+// The ConvGemmArgs of the launch, its weight images and its plan, finished by the same statements for the real call and for the query
+// (query: every image is a probe pointer, nothing is launched and no device is touched).  ln: launch_conv_gemm_ln's arguments.
+namespace {
+struct EpiLaunch {
+  int dt = F32;
+  ConvGemmArgs a;
+  ConvGemmPlan pl;
+  bool rowpart = false, gnpart = false;
+};
+int64_t epi_workspace_bytes(const sf_conv1d_epi_desc &d) {
+  const int64_t K = (int64_t)d.taps * d.C + d.C2;
+  return 16 * (int64_t)d.N * K + 4 * (int64_t)d.N + 8 * 256;   // w, wfr (compute type), wx, wfrx (4 bytes per element), the column sums
+}
+EpiLaunch epi_build(const sf_conv1d_epi_desc &d, bool ln, bool query, void *ws, int64_t ws_bytes, hipStream_t s) {
+  if (d.dtype != SF_F32 && d.dtype != SF_BF16 && d.dtype != SF_F16 && d.dtype != SF_F32X) fail(SF_ERR_INVALID, "unknown dtype %d", d.dtype);
+  if (d.B < 1 || d.L < 1 || d.C < 1 || d.C2 < 0 || d.N < 1 || d.taps < 1 || d.stride < 1 || d.pad < 0 || d.upsample < 1 ||
+      (int64_t)d.L * d.upsample + 2 * d.pad < d.taps)
+    fail(SF_ERR_INVALID, "bad geometry");
+  if (d.upsample & (d.upsample - 1)) fail(SF_ERR_UNSUPPORTED, "upsample must be a power of two");
+  if ((d.C % 32) || (d.C2 % 32)) fail(SF_ERR_UNSUPPORTED, "C and C2 must be multiples of 32 (the thin path has no such epilogue)");
+  if (d.C2 > 0 && d.taps != 1) fail(SF_ERR_UNSUPPORTED, "a second source needs taps == 1");
+  if (d.act < 0 || d.act > 3) fail(SF_ERR_UNSUPPORTED, "act must be 0 .. 3");
+  const int Lout = (d.L * d.upsample + 2 * d.pad - d.taps) / d.stride + 1;
+  const int64_t M64 = (int64_t)d.B * Lout, K64 = (int64_t)d.taps * d.C + d.C2;
+  if (M64 > 0x7FFFFFFF || K64 > 0x7FFFFFFF) fail(SF_ERR_UNSUPPORTED, "more than 2^31 rows");
+  if (!query) {
+    if (!d.x || !d.w || !d.out || !ws || (d.C2 > 0 && !d.x2)) fail(SF_ERR_INVALID, "null argument");
+    if (ws_bytes < epi_workspace_bytes(d)) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)epi_workspace_bytes(d));
+  }
+  if (reinterpret_cast<uintptr_t>(d.w) % 16) fail(SF_ERR_INVALID, "w must be 16-byte aligned");
+  EpiLaunch r;
+  const bool x3 = d.dtype == SF_F32X;
+  const int dt = r.dt = x3 ? F32 : d.dtype;
+  const int N = d.N, K = (int)K64;
+  Workspace wk(ws, ws_bytes);
+  ConvGemmArgs &a = r.a;
+  a.src = d.x;
+  a.src_ld = d.C;
+  a.src2 = d.C2 ? d.x2 : nullptr;
+  a.src2_ld = d.C2;
+  a.bias = d.bias;
+  a.N = a.n_store = N;
+  a.K = K;
+  a.cin = d.C;
+  a.cin2 = d.C2;
+  a.taps = d.taps;
+  a.stride = d.stride;
+  a.pad = d.pad;
+  while ((1 << a.up_shift) < d.upsample) ++a.up_shift;
+  a.Lsrc = d.L;
+  a.Lout = Lout;
+  a.M = (int)M64;
+  a.out = d.out;
+  a.out_ld = N;
+  a.res = d.residual;
+  a.res_ld = N;
+  a.bscale = d.bscale;
+  a.bscale_ld = N;
+  a.badd = d.badd;
+  a.badd_ld = N;
+  a.act = d.act;
+  a.out_f32 = d.out_f32 ? 1 : 0;
+  a.solo = d.solo ? 1 : 0;
+  a.mt_ln = d.mt_ln ? 1 : 0;
+  // ---- weight images, as the engine packs them; the LayerNorm consumer's column sums ------------------------------------------------------
+  // Two passes of the same statements: probe pointers first (only whether an image exists enters a plan), so that the entry can refuse
+  // before anything is launched; the real images are allocated and packed behind the plan (real = true).
+  if (ln) {
+    if (!d.ln_part) fail(SF_ERR_INVALID, "ln_part is required");
+    if (d.ln_operand == 0 && (d.ln_ss || d.res_ln)) fail(SF_ERR_INVALID, "the accumulator-side form takes no ln_ss / res_ln");
+  } else if (d.ln_part || d.ln_ss || d.res_ln) {
+    fail(SF_ERR_INVALID, "LayerNorm arguments on the plain launch (sf_op_conv1d_ln takes them)");
+  }
+  auto set_images = [&](bool real) {
+    auto image = [&](int64_t bytes) -> void * { return real ? wk.alloc(bytes) : reinterpret_cast<void *>(256); };
+    const void *wp = d.w;   // fp32: the caller's matrix is the GEMM's
+    if (dt != F32) {
+      void *packed = image((int64_t)N * K * 2);
+      if (real) SF_HIP(launch_pack_rows(dt, d.w, N, K, K, nullptr, packed, K, s));
+      wp = packed;
+      if ((K % 64) == 0 && K <= 2048 && (N % 32) == 0) {   // fragment order for the register-staged kernel (conv_gemm_rs.hip)
+        void *wfr = image((int64_t)N * K * 2);
+        if (real) SF_HIP(launch_pack_wfr(dt, wp, N, K, wfr, s));
+        a.wfr = wfr;
+      }
+    } else if (x3 && (K % 32) == 0) {
+      void *wx = image((int64_t)N * K * 4);
+      if (real) SF_HIP(launch_pack_wx(static_cast<const float *>(wp), N, K, wx, s));
+      a.wx = wx;
+      if ((K % 64) == 0 && K <= 1280 && (N % 32) == 0) {
+        void *wfrx = image((int64_t)N * K * 4);
+        if (real) SF_HIP(launch_pack_wfrx(static_cast<const float *>(wp), N, K, wfrx, s));
+        a.wfrx = wfrx;
+      }
+    }
+    a.w = wp;
+    if (ln && d.ln_operand == 0) {
+      float *colsum = static_cast<float *>(image((int64_t)N * 4));
+      if (real) SF_HIP(launch_row_sums(dt, wp, N, K, colsum, s));
+      a.ln_colsum = colsum;
+    }
+  };
+  set_images(false);
+  if (ln) {
+    a.ln_part = d.ln_part;
+    a.ln_nt = d.C / 32;
+    a.ln_eps = d.ln_eps;
+    if (d.ln_operand != 0) {
+      a.ln_ss = d.ln_ss;
+      a.ln_ss_ld = 2 * d.C;
+      a.res_ln = d.res_ln ? 1 : 0;
+    }
+  }
+  // ---- statistics outputs: armed, and kept only where the plan honours them -------------------------------------------------------------------
+  const bool stats_ok = (N % 32) == 0;
+  if (d.rowpart && stats_ok) {
+    a.rowpart_out = d.rowpart;
+    a.rowpart_nt = N / 32;
+  }
+  if (d.gnpart && stats_ok && !ln) a.gnpart_out = d.gnpart;
+  auto plan = [&] { return ln ? conv_gemm_ln_plan(dt, a) : conv_gemm_plan(dt, a); };
+  r.pl = plan();
+  if (a.rowpart_out && !r.pl.rowpart) {
+    a.rowpart_out = nullptr;
+    a.rowpart_nt = 0;
+  }
+  if (a.gnpart_out && !r.pl.gnpart) a.gnpart_out = nullptr;
+  r.pl = plan();
+  if (r.pl.family == CG_INVALID || !conv_gemm_supported(dt, a)) fail(SF_ERR_UNSUPPORTED, "no GEMM kernel takes these arguments");
+  if ((a.rowpart_out && !r.pl.rowpart) || (a.gnpart_out && !r.pl.gnpart)) fail(SF_ERR_UNSUPPORTED, "the plan moved when a declined output was disarmed");
+  r.rowpart = a.rowpart_out != nullptr;
+  r.gnpart = a.gnpart_out != nullptr;
+  if (!query) {   // the launch is decided and will not be refused: now the images (the plan read only which of them exist)
+    const ConvGemmPlan probe = r.pl;
+    set_images(true);
+    r.pl = plan();
+    if (r.pl.family != probe.family || r.pl.tile != probe.tile || r.pl.split != probe.split) fail(SF_ERR_INVALID, "the plan depends on an image's address");
+  }
+  return r;
+}
+int epi_variant(const sf_conv1d_epi_desc *d, bool ln, char *label, int label_bytes, int *rowpart_done, int *gnpart_done) {
+  SF_API_BEGIN
+  if (!d || !label || label_bytes < 1) fail(SF_ERR_INVALID, "null argument");
+  label[0] = 0;
+  const EpiLaunch r = epi_build(*d, ln, true, nullptr, 0, nullptr);
+  snprintf(label, (size_t)label_bytes, "%s", r.pl.label);
+  if (rowpart_done) *rowpart_done = r.rowpart ? 1 : 0;
+  if (gnpart_done) *gnpart_done = r.gnpart ? 1 : 0;
+  return SF_OK;
+  SF_API_END
+}
+}  // namespace
+
+int64_t sf_op_conv1d_epi_workspace_bytes(const sf_conv1d_epi_desc *d) {
+  if (!d || d->C < 1 || d->C2 < 0 || d->N < 1 || d->taps < 1) return -1;
+  return epi_workspace_bytes(*d);
+}
+
+int sf_op_conv1d_epi(const sf_conv1d_epi_desc *d, int *rowpart_done, int *gnpart_done, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!d) fail(SF_ERR_INVALID, "null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const EpiLaunch r = epi_build(*d, false, false, ws, ws_bytes, s);
+  if (rowpart_done) *rowpart_done = r.rowpart ? 1 : 0;
+  if (gnpart_done) *gnpart_done = r.gnpart ? 1 : 0;
+  SF_HIP(launch_conv_gemm_planned(r.dt, r.a, r.pl, s));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_conv1d_epi_variant(const sf_conv1d_epi_desc *d, char *label, int label_bytes, int *rowpart_done, int *gnpart_done) {
+  return epi_variant(d, false, label, label_bytes, rowpart_done, gnpart_done);
+}
+
+int sf_op_conv1d_ln(const sf_conv1d_epi_desc *d, int *rowpart_done, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!d) fail(SF_ERR_INVALID, "null argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const EpiLaunch r = epi_build(*d, true, false, ws, ws_bytes, s);
+  if (rowpart_done) *rowpart_done = r.rowpart ? 1 : 0;
+  SF_HIP(launch_conv_gemm_planned(r.dt, r.a, r.pl, s));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_conv1d_ln_variant(const sf_conv1d_epi_desc *d, char *label, int label_bytes, int *rowpart_done) {
+  return epi_variant(d, true, label, label_bytes, rowpart_done, nullptr);
+}
+
+// ---- sf_op_conv_cb_tiles: the channel-block convolution behind the TILE statistics of a producing GEMM (conv_cb prologue 2) ----------------
+int64_t sf_op_conv_cb_tiles_workspace_bytes(int dtype, int B, int L, int C) {
+  if (B < 1 || L < 1 || C < 1 || (dtype != SF_BF16 && dtype != SF_F16 && dtype != SF_F32X)) return -1;
+  Workspace dry(nullptr, 0);
+  dry.alloc((int64_t)C * C * 3 * (int64_t)dsize(dtype));       // fragment-ordered weights
+  dry.alloc((int64_t)(C / 128) * B * L * C * 4);               // the partial slabs
+  return dry.used();
+}
+
+int sf_op_conv_cb_tiles(int dtype, const void *x, const float *w, const float *bias, const float *gn_g, const float *gn_b, int groups, float eps,
+                        const float *tile_stats, int B, int L, int C, void *h_out, float *stats_out, int *nch_out, int *chunk_rows_out, void *ws,
+                        int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!x || !w || !bias || !gn_g || !gn_b || !tile_stats || !h_out || !stats_out || !ws) fail(SF_ERR_INVALID, "null argument");
+  if (dtype != SF_BF16 && dtype != SF_F16 && dtype != SF_F32X) fail(SF_ERR_UNSUPPORTED, "bf16, fp16 or fp32x");
+  if (B < 1 || L < 1 || C < 1 || groups < 1 || groups > 64 || !conv_cb_shape_ok(dtype, B, L, C, C, groups) || !conv_cb_tile_stats_ok(L, C, groups))
+    fail(SF_ERR_UNSUPPORTED, "shape outside the tile-statistics prologue of the channel-block convolution");
+  const int64_t need = sf_op_conv_cb_tiles_workspace_bytes(dtype, B, L, C);
+  if (ws_bytes < need) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes", (long long)need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  Workspace wk(ws, ws_bytes);
+  const int64_t M = (int64_t)B * L;
+  const int S = C / 128;
+  const int adt = dtype == SF_F32X ? (int)F32 : dtype;   // activations and the reducer of the fp32x chain are plain fp32
+  void *wp = wk.alloc((int64_t)C * C * 3 * (int64_t)dsize(dtype));
+  float *slab = static_cast<float *>(wk.alloc((int64_t)S * M * C * 4));
+  const CbGnPlan gp = cb_gn_plan(L);
+  if (gp.nch > 32) fail(SF_ERR_UNSUPPORTED, "more than 32 statistics chunks per clip");
+  if (nch_out) *nch_out = gp.nch;
+  if (chunk_rows_out) *chunk_rows_out = gp.chunk_rows;
+  SF_HIP(launch_pack_conv_cb(dtype, w, C, C, wp, s));
+  ConvCbArgs a;
+  a.src = x;
+  a.src_ld = C;
+  a.wp = wp;
+  a.slab = slab;
+  a.B = B;
+  a.L = L;
+  a.C = a.N = C;
+  a.pro = 2;
+  a.G = groups;
+  a.stats = tile_stats;
+  a.gamma = gn_g;
+  a.beta = gn_b;
+  a.eps = eps;
+  SF_HIP(launch_conv_cb(dtype, a, s));
+  SF_HIP(launch_cb_reduce_gn(adt, slab, S, B, L, C, bias, h_out, C, groups, stats_out, gp, s));
+  return SF_OK;
+  SF_API_END
+}
+
 // Timing aid: the four launches of the channel-block chain, each averaged over `iters` back-to-back launches on random data
 // (ms[0] conv_cb without prologue, ms[1] cb_reduce_gn, ms[2] conv_cb with the GroupNorm+SiLU prologue, ms[3] cb_reduce_ln).
 // cold != 0: rotate through enough weight copies that every launch streams its weights from HBM.

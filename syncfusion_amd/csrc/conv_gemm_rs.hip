@@ -201,8 +201,13 @@ __global__ __launch_bounds__(256) void conv_gemm_rs_kernel(const void *const wim
       av[e] = ea[e];
       cu[e] = ec[e];
       rv[e] = has_res ? to_f(rt[e]) : 0.f;
-      ln_mp[e] = __builtin_bit_cast(float, lp[e][0]);
-      ln_qp[e] = __builtin_bit_cast(float, lp[e][1]);
+      // (mean, M2) through a copy of the pair.  __builtin_bit_cast takes the ADDRESS of its operand, and an element of an ext_vector has
+      // none of its own: bit_cast(float, lp[e][1]) read from the vector's base, element 0 -- a dword load and M2 = mean in the ISA -- so the
+      // variance pooled here was that of the partial means alone plus mean / 32.  Never bit_cast an indexed vector element
+      float pm[2];
+      __builtin_memcpy(pm, &lp[e], 8);
+      ln_mp[e] = pm[0];
+      ln_qp[e] = pm[1];
     }
   }
 
