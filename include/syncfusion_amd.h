@@ -849,6 +849,76 @@ int sf_clap_text_forward(sf_clap_text *h, const int32_t *ids, const int32_t *mas
                          int64_t ws_bytes, void *stream);
 int sf_clap_text_describe(const sf_clap_text_config *cfg, int B, int S, char *text /*host*/, int64_t capacity);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG frames on the device (syncfusion_amd/jpeg.py)
+ *   replaces: PIL.Image.open(path).convert("RGB") of main/dataset_onset.py:155 for the files script/gh_preprocess_videos.py:122-123
+ *   writes (baseline sequential, one interleaved scan).  The output is libjpeg's default decode, byte for byte: Huffman decode, the
+ *   integer "islow" IDCT, fancy h2v1 / h2v2 chroma upsampling, integer YCbCr -> RGB.  Exact for streams an encoder writes (IDCT
+ *   outputs inside +-512 around the level shift); beyond that the result is clamped and unspecified.
+ *
+ * sf_jpeg_parse   HOST only (no HIP call).  bytes: the N files back to back; offsets: N + 1 positions, file i is
+ *     bytes[offsets[i] .. offsets[i + 1]).  Fills one descriptor per file and, when segs_out is given, the segment table: a file
+ *     without a restart interval is one segment, otherwise every restart interval is one (DC prediction restarts there, so segments
+ *     decode independently); the count per file follows from its header, ceil(MCUs / interval), the RSTn markers are found by a byte
+ *     scan, and the last segment of a file runs to the end of its entropy-coded data.  desc.status says what the device may do with
+ *     the file: SF_JPEG_OK; SF_JPEG_UNSUPPORTED (a valid stream outside the kernels' coverage, desc.reason names why: progressive,
+ *     arithmetic, lossless or 12-bit frames, 2 or 4 components, several scans, Huffman table ids above 1, sampling other than luma
+ *     1x1 / 2x1 / 2x2 over 1x1 chroma, an Adobe marker with transform != 1, component ids R G B) or SF_JPEG_MALFORMED (desc.reason
+ *     names the defect).  Unsupported and malformed files have no segments and take no workspace.  coef_offset / plane_offset are
+ *     the file's places in the workspace of ONE decode call over exactly these N descriptors.  *n_segs_out: the segment count.
+ *     Returns SF_ERR_WORKSPACE when seg_capacity is below it (descriptors are complete, no segment is written), SF_ERR_INVALID
+ *     when a file is malformed (the first one is named in the message; all descriptors are complete), SF_OK otherwise.  No byte
+ *     outside bytes[offsets[0] .. offsets[N]) is read, whatever the files hold.
+ * sf_jpeg_decode_workspace_bytes   HOST only: the workspace of one decode call over these descriptors (-1: bad argument) --
+ *     int16 coefficient blocks in natural order, each component padded to whole MCUs, then the uint8 component planes of the same
+ *     padded extent.
+ * sf_jpeg_decode   bytes_dev: the same bytes on the device (n_bytes = offsets[N], offsets[0] = 0); desc_host / desc_dev: the
+ *     descriptors as the parser filled them, on the host (checked before any launch: sizes, sampling, table selectors, offsets and
+ *     ranges) and the same bytes on the device; segs_dev: the segment table on the device.  Every SF_JPEG_OK file must be
+ *     width x height = W x H.  out: (N, H, W, 3) uint8; the slots of files that are not SF_JPEG_OK are written as zeros.
+ *     status_dev: N int32, zeroed by the call, then the first problem the entropy decoder met per file (SF_JPEG_ST_*); a flagged file
+ *     leaves the others alone, its own pixels are unspecified.  The call zeroes what it needs of the workspace.  One wave per
+ *     segment; no read outside bytes_dev[0 .. n_bytes), no write outside a wave's own blocks, for any bytes.  Nothing synchronises.
+ * ---------------------------------------------------------------------------------------- */
+enum { SF_JPEG_OK = 0, SF_JPEG_UNSUPPORTED = 1, SF_JPEG_MALFORMED = 2 };
+enum {
+  SF_JPEG_ST_OUT_OF_BITS = 1,     /* the segment ended (or a marker came) before its MCUs were complete */
+  SF_JPEG_ST_BAD_CODE = 2,        /* a bit pattern no Huffman code of the table matches, or a DC category above 15 */
+  SF_JPEG_ST_INDEX_OVERFLOW = 3,  /* a run past coefficient 63 */
+  SF_JPEG_ST_TRAILING_BYTES = 4,  /* bytes left in the segment behind its last MCU */
+  SF_JPEG_ST_BAD_SEGMENT = 5      /* a segment table entry outside its file or its MCUs */
+};
+typedef struct {
+  int32_t status;              /* SF_JPEG_OK / SF_JPEG_UNSUPPORTED / SF_JPEG_MALFORMED */
+  int32_t width, height, ncomp;
+  int32_t h[3], v[3];          /* sampling factors (1 x 1 for a one-component file, whatever its header says) */
+  int32_t tq[3], td[3], ta[3]; /* quantisation / DC / AC table selectors */
+  int32_t restart_interval;    /* MCUs, 0: none */
+  int32_t mcus_x, mcus_y;
+  int32_t quant_precision[4];  /* -1: absent, 0: 8-bit, 1: 16-bit */
+  int32_t huff_present;        /* bit 0, 1: DC tables 0, 1; bit 2, 3: AC tables 0, 1 */
+  int32_t seg_count;
+  int64_t seg_begin;           /* first entry of this file in the segment table */
+  int64_t data_begin, data_end;/* entropy-coded bytes, positions in the concatenated buffer */
+  int64_t coef_offset;         /* int16 elements from the start of the workspace */
+  int64_t plane_offset;        /* bytes from the start of the plane area of the workspace */
+  int64_t reserved;            /* (keeps quant, and an array of descriptors, on 16-byte boundaries) */
+  uint16_t quant[4][64];       /* natural (de-zigzagged) order */
+  uint8_t huff_counts[4][16];  /* [0], [1]: DC tables 0, 1; [2], [3]: AC tables 0, 1 */
+  uint8_t huff_values[4][256];
+  char reason[64];
+} sf_jpeg_desc;
+typedef struct {
+  int32_t image, first_mcu, mcu_count, reserved;
+  int64_t byte_begin, byte_end; /* positions in the concatenated buffer; the RSTn marker behind the segment is outside */
+} sf_jpeg_segment;
+int sf_jpeg_parse(const uint8_t *bytes /*host*/, const int64_t *offsets /*host*/, int N, sf_jpeg_desc *desc_out /*host*/,
+                  sf_jpeg_segment *segs_out /*host*/, int64_t seg_capacity, int64_t *n_segs_out /*host*/);
+int64_t sf_jpeg_decode_workspace_bytes(const sf_jpeg_desc *desc /*host*/, int N);
+int sf_jpeg_decode(const uint8_t *bytes_dev, int64_t n_bytes, const sf_jpeg_desc *desc_host, const sf_jpeg_desc *desc_dev,
+                   const sf_jpeg_segment *segs_dev, int64_t n_segs, int N, int H, int W, uint8_t *out, int32_t *status_dev, void *ws,
+                   int64_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

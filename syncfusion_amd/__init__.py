@@ -6,7 +6,7 @@ Public surface = the reference's own: ``DiffusionModel`` 
 runs in ``lib/libsyncfusion_amd.so`` (hand-written HIP, C ABI in include/syncfusion_amd.h).
 """
 from . import _lib  # noqa: F401
-from . import audio_features, autograd, clap, clap_text, evaluation, fad, frame_transforms, onset_test, onset_training, shards, training, video_chunks  # noqa: F401
+from . import audio_features, autograd, clap, clap_text, evaluation, fad, frame_transforms, jpeg, onset_test, onset_training, shards, training, video_chunks  # noqa: F401
 from .config import instantiate, instantiate_class, instantiate_frames_transforms, instantiate_model_yaml
 from .diffusion import DiffusionModel, LinearSchedule, UNetV0, VDiffusion, VInpainter, VSampler
 from .audio_features import MelSpectrogram, mel_filterbank, onset_detect, onset_strength
@@ -15,12 +15,14 @@ from .evaluation import evaluate_onsets
 from .clap import ClapAudioConfig, ClapAudioEmbedder
 from .clap_text import ClapEmbedder, ClapTextConfig, ClapTokenizer
 from .fad import VGGish, VGGishConfig, embedding_statistics, evaluate_fad, frechet_distance
+from .jpeg import JpegInfo, decode_jpeg_batch, parse_jpeg
 from .generation import (generate_batch, generate_dataset, generate_long, inpaint_batch, long_windows, prepare_gt_for_fad,
                          regions_to_keep_mask)
 from .module import Model, RandomEmbedder
 from .module_onset import Model as OnsetModel
 from .onset_net import VideoOnsetNet
 from .onset_test import OnsetTestStage, annotation_rows, pack_onset_preds, test_onset_model
+from .video_chunks import run_onset_test
 from .onset_training import GraphedOnsetTrainStep
 from .onset_glue import cut_prefix_crop, onsets_to_track
 from .resample import resample
@@ -33,5 +35,6 @@ __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule
            "fad", "VGGish", "VGGishConfig", "embedding_statistics", "frechet_distance", "evaluate_fad",
            "VInpainter", "inpaint_batch", "generate_long", "long_windows", "regions_to_keep_mask",
            "onset_test", "OnsetTestStage", "annotation_rows", "pack_onset_preds", "test_onset_model", "prepare_gt_for_fad",
+           "jpeg", "JpegInfo", "decode_jpeg_batch", "parse_jpeg", "run_onset_test",
            "clap", "ClapAudioConfig", "ClapAudioEmbedder", "clap_text", "ClapEmbedder", "ClapTextConfig", "ClapTokenizer"]
 __version__ = "0.1.0"

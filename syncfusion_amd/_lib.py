@@ -78,6 +78,23 @@ class ClapTextEngineConfig(C.Structure):
                [("ln_eps", C.c_float), ("pooling", C.c_int32), ("projection_relu", C.c_int32), ("normalize", C.c_int32)]
 
 
+class JpegDesc(C.Structure):
+    """sf_jpeg_desc: what the parser says about one JPEG file (syncfusion_amd/jpeg.py)."""
+    _fields_ = [("status", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32),
+                ("h", C.c_int32 * 3), ("v", C.c_int32 * 3), ("tq", C.c_int32 * 3), ("td", C.c_int32 * 3), ("ta", C.c_int32 * 3),
+                ("restart_interval", C.c_int32), ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("quant_precision", C.c_int32 * 4),
+                ("huff_present", C.c_int32), ("seg_count", C.c_int32), ("seg_begin", C.c_int64), ("data_begin", C.c_int64),
+                ("data_end", C.c_int64), ("coef_offset", C.c_int64), ("plane_offset", C.c_int64), ("reserved", C.c_int64),
+                ("quant", (C.c_uint16 * 64) * 4), ("huff_counts", (C.c_uint8 * 16) * 4), ("huff_values", (C.c_uint8 * 256) * 4),
+                ("reason", C.c_char * 64)]
+
+
+class JpegSegment(C.Structure):
+    """sf_jpeg_segment: one independently decodable stretch of entropy-coded bytes."""
+    _fields_ = [("image", C.c_int32), ("first_mcu", C.c_int32), ("mcu_count", C.c_int32), ("reserved", C.c_int32),
+                ("byte_begin", C.c_int64), ("byte_end", C.c_int64)]
+
+
 # every symbol include/syncfusion_amd.h declares: (restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -281,6 +298,12 @@ SYMBOLS = {
     "sf_clap_text_forward": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _L, _P]),
     # (cfg, B, S, text_host, capacity)
     "sf_clap_text_describe": (_I, [C.POINTER(ClapTextEngineConfig), _I, _I, C.c_char_p, _L]),
+    # JPEG frames on the device (syncfusion_amd/jpeg.py)
+    # (bytes_host, offsets_host, N, desc_out, segs_out, seg_capacity, n_segs_out)
+    "sf_jpeg_parse": (_I, [_P, _P, _I, _P, _P, _L, C.POINTER(_L)]),
+    "sf_jpeg_decode_workspace_bytes": (_L, [_P, _I]),
+    # (bytes_dev, n_bytes, desc_host, desc_dev, segs_dev, n_segs, N, H, W, out, status_dev, ws, ws_bytes, stream)
+    "sf_jpeg_decode": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _L, _P]),
 }
 
 _lib: Optional[C.CDLL] = None
