@@ -482,11 +482,15 @@ int sf_op_inject_prenorm_proj(int dtype, const void *m, const void *ctx, const f
  * Both launches size their workspace with sf_op_conv1d_epi_workspace_bytes.  Every entry refuses with SF_ERR_UNSUPPORTED before anything is
  * launched (the weight images are packed behind the plan) where no kernel takes the arguments.  The _variant queries need
  * no device and take no data pointers' contents: only whether an optional pointer is set enters the plan; they return the label of the
- * kernel and the flags from the same finished launch arguments as the real call. */
+ * kernel and the flags from the same finished launch arguments as the real call.
+ * src_x3 != 0 (sf_op_conv1d_epi and its query only): x holds pre-split rows, as a producer with xfmt writes them (sf_op_gn_silu_rows below):
+ * row m is C * 4 bytes, [C / 32][hi 32 x fp16 | lo' 32 x fp16] with hi = fp16(v), lo' = fp16((v - hi) * 2048).  Honoured only by the
+ * macro-tile kernel on SF_F32X with C2 == 0: every other dtype, a second source, or a shape whose plan does not read pre-split rows is
+ * SF_ERR_UNSUPPORTED before anything is packed or launched, from the launch and from the query alike. */
 typedef struct {
   int32_t dtype, B, L, C, C2, N, taps, stride, pad, upsample, act, out_f32, mt_ln, res_ln, ln_operand, solo;
   float ln_eps;
-  int32_t reserved;
+  int32_t src_x3;
   const void *x, *x2;
   const float *w, *bias, *bscale, *badd;
   const void *residual;
@@ -522,6 +526,20 @@ int sf_op_ln_modulate(int dtype, const void *x, const float *scale_shift /* (B, 
                       int B, int L, int C, void *out, void *stream);
 /* multi-head attention on packed projections: q:(B,L,H*D), kv:(B,L,2*H*D) -> out:(B,L,H*D) */
 int sf_op_attention(int dtype, const void *q, const void *kv, int B, int L, int heads, int head_dim, void *out, void *stream);
+/* The three operations above as the engine launches them in front of a GEMM, with the output row stride and the row format exposed.
+ * xfmt != 0: the output rows are written pre-split for a GEMM that takes sf_conv1d_epi_desc::src_x3 (the layout is described there)
+ * instead of as floats; the buffer has the same size either way.  What the launcher does not take is SF_ERR_UNSUPPORTED before anything
+ * is launched: with xfmt, any dtype but SF_F32 (norms) / SF_F32X (attention), C % 32 != 0, out_ld != C (ldo != heads * head_dim),
+ * (C / groups) % 4 != 0.
+ * sf_op_attention_rows takes the row strides of q, kv and out in elements: kv points at the row's keys, its values follow heads * head_dim
+ * columns later, and kv may point into the buffer q points into (the engine's packed q | k | v rows: ldq = ldkv = 3 * heads * head_dim,
+ * kv = q + heads * head_dim). */
+int sf_op_gn_silu_rows(int dtype, const void *x, const float *gamma, const float *beta, int groups, float eps, int B, int L, int C, void *out,
+                       int out_ld, int xfmt, void *stream);
+int sf_op_ln_modulate_rows(int dtype, const void *x, const float *scale_shift /* (B, 2C) or NULL */, float eps, int B, int L, int C, void *out,
+                           int out_ld, int xfmt, void *stream);
+int sf_op_attention_rows(int dtype, const void *q, int ldq, const void *kv, int ldkv, int B, int L, int heads, int head_dim, void *out, int ldo,
+                         int xfmt, void *stream);
 
 
 /* ---- VideoOnsetNet training (fp32; main/module_onset.py trains main/onset_net.py:46-63 in fp32) ----------------------------------------

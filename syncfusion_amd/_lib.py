@@ -57,7 +57,7 @@ class Conv1dEpiDesc(C.Structure):
     """sf_conv1d_epi_desc: one implicit-GEMM launch with its whole epilogue (sf_op_conv1d_epi / sf_op_conv1d_ln)."""
     _fields_ = [(n, C.c_int32) for n in ("dtype", "B", "L", "C", "C2", "N", "taps", "stride", "pad", "upsample", "act", "out_f32", "mt_ln", "res_ln",
                                          "ln_operand", "solo")] + \
-               [("ln_eps", C.c_float), ("reserved", C.c_int32)] + \
+               [("ln_eps", C.c_float), ("src_x3", C.c_int32)] + \
                [(n, C.c_void_p) for n in ("x", "x2", "w", "bias", "bscale", "badd", "residual", "out", "rowpart", "gnpart", "ln_part", "ln_ss")]
 
 
@@ -204,6 +204,13 @@ SYMBOLS = {
     "sf_bench_conv_cb": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float)]),
     "sf_op_ln_modulate": (_I, [_I, _P, _P, _F, _I, _I, _I, _P, _P]),
     "sf_op_attention": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    # the same launchers with the output stride and the pre-split row format (xfmt) exposed
+    # (dtype, x, gamma, beta, groups, eps, B, L, C, out, out_ld, xfmt, stream)
+    "sf_op_gn_silu_rows": (_I, [_I, _P, _P, _P, _I, _F, _I, _I, _I, _P, _I, _I, _P]),
+    # (dtype, x, scale_shift, eps, B, L, C, out, out_ld, xfmt, stream)
+    "sf_op_ln_modulate_rows": (_I, [_I, _P, _P, _F, _I, _I, _I, _P, _I, _I, _P]),
+    # (dtype, q, ldq, kv, ldkv, B, L, heads, head_dim, out, ldo, xfmt, stream)
+    "sf_op_attention_rows": (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     # VideoOnsetNet training (fp32, channels-last video rows)
     "sf_op_vconv_workspace_bytes": (_L, [C.POINTER(VConvDesc)]),
     "sf_op_vconv_fwd": (_I, [C.POINTER(VConvDesc), _P, _P, _P, _P, _L, _P]),

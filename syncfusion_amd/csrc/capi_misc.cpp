@@ -861,6 +861,7 @@ EpiLaunch epi_build(const sf_conv1d_epi_desc &d, bool ln, bool query, void *ws, 
   if ((d.C % 32) || (d.C2 % 32)) fail(SF_ERR_UNSUPPORTED, "C and C2 must be multiples of 32 (the thin path has no such epilogue)");
   if (d.C2 > 0 && d.taps != 1) fail(SF_ERR_UNSUPPORTED, "a second source needs taps == 1");
   if (d.act < 0 || d.act > 3) fail(SF_ERR_UNSUPPORTED, "act must be 0 .. 3");
+  if (d.src_x3 && (ln || d.dtype != SF_F32X || d.C2 != 0)) fail(SF_ERR_UNSUPPORTED, "src_x3: pre-split rows are one fp32x source of the plain launch");
   const int Lout = (d.L * d.upsample + 2 * d.pad - d.taps) / d.stride + 1;
   const int64_t M64 = (int64_t)d.B * Lout, K64 = (int64_t)d.taps * d.C + d.C2;
   if (M64 > 0x7FFFFFFF || K64 > 0x7FFFFFFF) fail(SF_ERR_UNSUPPORTED, "more than 2^31 rows");
@@ -903,6 +904,7 @@ EpiLaunch epi_build(const sf_conv1d_epi_desc &d, bool ln, bool query, void *ws, 
   a.out_f32 = d.out_f32 ? 1 : 0;
   a.solo = d.solo ? 1 : 0;
   a.mt_ln = d.mt_ln ? 1 : 0;
+  a.src_x3 = d.src_x3 ? 1 : 0;
   // ---- weight images, as the engine packs them; the LayerNorm consumer's column sums ------------------------------------------------------
   // Two passes of the same statements: probe pointers first (only whether an image exists enters a plan), so that the entry can refuse
   // before anything is launched; the real images are allocated and packed behind the plan (real = true).
@@ -968,6 +970,7 @@ EpiLaunch epi_build(const sf_conv1d_epi_desc &d, bool ln, bool query, void *ws, 
   if (a.gnpart_out && !r.pl.gnpart) a.gnpart_out = nullptr;
   r.pl = plan();
   if (r.pl.family == CG_INVALID || !conv_gemm_supported(dt, a)) fail(SF_ERR_UNSUPPORTED, "no GEMM kernel takes these arguments");
+  if (a.src_x3 && !r.pl.src_x3) fail(SF_ERR_UNSUPPORTED, "src_x3: the plan (%s) does not read pre-split rows", r.pl.label);
   if ((a.rowpart_out && !r.pl.rowpart) || (a.gnpart_out && !r.pl.gnpart)) fail(SF_ERR_UNSUPPORTED, "the plan moved when a declined output was disarmed");
   r.rowpart = a.rowpart_out != nullptr;
   r.gnpart = a.gnpart_out != nullptr;
@@ -1164,6 +1167,55 @@ int sf_op_attention(int dtype, const void *q, const void *kv, int B, int L, int 
   const bool x3 = dtype == SF_F32X;   // fp32 tensors, products from split fp16 operands
   SF_HIP(launch_attention(x3 ? (int)F32 : dtype, q, heads * head_dim, kv, 2 * heads * head_dim, B, L, heads, head_dim, out, heads * head_dim,
                           static_cast<hipStream_t>(stream), x3));
+  return SF_OK;
+  SF_API_END
+}
+
+// ---- the same three launchers as the engine calls them in front of a GEMM: output stride and row format exposed (tests/x3rows_ref.py) ------
+namespace {
+// hipErrorInvalidValue is a launcher's own refusal, returned before it launches anything
+void launched(hipError_t e, const char *launcher) {
+  if (e == hipErrorInvalidValue) fail(SF_ERR_UNSUPPORTED, "%s does not take these arguments", launcher);
+  if (e != hipSuccess) fail(SF_ERR_HIP, "%s -> %s", launcher, hipGetErrorString(e));
+}
+}  // namespace
+
+int sf_op_gn_silu_rows(int dtype, const void *x, const float *gamma, const float *beta, int groups, float eps, int B, int L, int C, void *out,
+                       int out_ld, int xfmt, void *stream) {
+  SF_API_BEGIN
+  if (!x || !gamma || !beta || !out) fail(SF_ERR_INVALID, "null argument");
+  if (dtype != SF_F32 && dtype != SF_BF16 && dtype != SF_F16) fail(SF_ERR_INVALID, "dtype must be SF_F32, SF_BF16 or SF_F16");
+  if (B < 1 || L < 1 || C < 1 || out_ld < C) fail(SF_ERR_INVALID, "bad geometry");
+  if (groups < 1 || C % groups) fail(SF_ERR_INVALID, "channels must be divisible by groups");
+  launched(launch_gn_silu(dtype, x, C, B, L, C, groups, gamma, beta, eps, out, out_ld, static_cast<hipStream_t>(stream), Prefetch(), xfmt != 0),
+           "launch_gn_silu");
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_ln_modulate_rows(int dtype, const void *x, const float *scale_shift, float eps, int B, int L, int C, void *out, int out_ld, int xfmt,
+                           void *stream) {
+  SF_API_BEGIN
+  if (!x || !out) fail(SF_ERR_INVALID, "null argument");
+  if (dtype != SF_F32 && dtype != SF_BF16 && dtype != SF_F16) fail(SF_ERR_INVALID, "dtype must be SF_F32, SF_BF16 or SF_F16");
+  if (B < 1 || L < 1 || C < 1 || out_ld < C) fail(SF_ERR_INVALID, "bad geometry");
+  launched(launch_ln_modulate(dtype, x, C, scale_shift, 2 * C, eps, B, L, C, out, out_ld, static_cast<hipStream_t>(stream), Prefetch(), xfmt != 0),
+           "launch_ln_modulate");
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_attention_rows(int dtype, const void *q, int ldq, const void *kv, int ldkv, int B, int L, int heads, int head_dim, void *out, int ldo,
+                         int xfmt, void *stream) {
+  SF_API_BEGIN
+  if (!q || !kv || !out) fail(SF_ERR_INVALID, "null argument");
+  if (dtype != SF_F32 && dtype != SF_BF16 && dtype != SF_F16 && dtype != SF_F32X) fail(SF_ERR_INVALID, "unknown dtype %d", dtype);
+  if (B < 1 || L < 1 || heads < 1 || head_dim < 1) fail(SF_ERR_INVALID, "bad geometry");
+  const int64_t hd = (int64_t)heads * head_dim;
+  if (ldq < hd || ldkv < 2 * hd || ldo < hd) fail(SF_ERR_INVALID, "a row stride is shorter than the row");
+  const bool x3 = dtype == SF_F32X;
+  launched(launch_attention(x3 ? (int)F32 : dtype, q, ldq, kv, ldkv, B, L, heads, head_dim, out, ldo, static_cast<hipStream_t>(stream), x3, xfmt != 0),
+           "launch_attention");
   return SF_OK;
   SF_API_END
 }
