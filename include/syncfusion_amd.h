@@ -698,6 +698,54 @@ int sf_onset_detect(sf_audio_features *h, const float *wav, int B, int L, float 
                     int32_t *positions, float *confidence, float *strength, void *ws, int64_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Complex STFT, inverse STFT and the spectral-gating denoiser (syncfusion_amd/denoise.py)
+ *   replaces: noisereduce.reduce_noise(x, sr, n_fft=1024, hop_length=256) of the --audio_denoise step at script/gh_preprocess_videos.py:91-100.
+ * All tensors fp32, contiguous, on the device.  A spectrum is stored (B, T, F, 2): F = n_fft / 2 + 1 interleaved complex bins per frame.
+ *
+ * sf_spectral_gate_create   HOST-only: checks the configuration and builds the periodic Hann window of win_length points (zeros behind it
+ *     up to n_fft, as scipy pads a frame at its END) and the twiddle table in fp64, rounded once.  n_fft: a power of two in [256, 4096];
+ *     2 <= win_length <= n_fft; hop >= 1; center != 0 pads win_length / 2 samples on each side of the clip (pad_mode 0 = zeros, 1 =
+ *     reflect) and gives T = (L + 2 (win_length / 2) - win_length) / hop + 1 frames, center == 0 gives T = (L - win_length) / hop + 1;
+ *     samples behind the last whole frame are not transformed.  scale_spectrum != 0 divides the bins by sum(w) (scipy's "spectrum") and the
+ *     inverse undoes it.  freq_taps / time_taps (host): the two odd-length factors of the separable mask filter, each summing to 1; {1}
+ *     is the identity.
+ * sf_spectral_gate_frames   T for a row of L samples; -1 for a null handle or L < win_length.
+ * sf_spectral_gate_workspace_bytes   one bound for every call below on (B, L) (-1 for a null handle, B < 1 or L < win_length);
+ *     for sf_istft_forward take L = win_length + (T - 1) hop - 2 pad.
+ * sf_stft_forward    wav (B, L) -> spec (B, T, F, 2).
+ * sf_istft_forward   spec (B, T, F, 2) -> out (B, out_len): per frame the inverse real transform (the imaginary parts of bins 0 and
+ *     n_fft / 2 do not enter), times the window; each output sample is the sum, in ascending frame order, of the frames that cover it
+ *     divided by the sum of their squared window values (1 where that sum is below 1e-10).  win_length + (T - 1) hop - 2 pad samples
+ *     exist; out is cut there or filled with zeros up to out_len.  hop need not divide win_length.
+ * sf_spectral_gate_noise_threshold   noise (B, L) -> thresh (B, F) = mean_t dB + n_std std_t dB (ddof 0, two passes) with
+ *     dB = 20 log10(max(|S|, 1e-20)) floored at the row's plane maximum - 80.
+ * sf_spectral_gate   the whole denoiser on B independent rows: spec = STFT(wav);
+ *     stationary == 0: sm = |spec| filtered forward and then backward over frames by y = smooth_b x + (1 - smooth_b) y_prev, each pass
+ *       started from its first input; mask_raw = sigmoid(((|spec| - sm) / sm - thresh_mult) slope), 0 where sm == 0;
+ *     stationary != 0: mask_raw = (dB > thresh[row, bin]) as 0 / 1;
+ *     mask_smooth = filter(mask_raw) prop_decrease + (1 - prop_decrease), or, with prop_before_smoothing != 0,
+ *       filter(mask_raw prop_decrease + (1 - prop_decrease)) (the two differ where the filter reaches outside the plane);
+ *     filter = freq_taps over bins, then time_taps over frames, zeros outside the plane;  out (B, L) = ISTFT(spec mask_smooth).
+ *     spec, mask_raw (B, T, F) and mask_smooth (B, T, F) are outputs as well.
+ * Refused before any HIP call: null pointers, B < 1, L < 1, n_std < 0, smooth_b outside (0, 1], prop_decrease outside [0, 1], and in the
+ * two calls that invert a window / hop pair that violates NOLA (min over n < hop of sum_k w[n + k hop]^2 <= 1e-10, evaluated in fp64 at
+ * create) (SF_ERR_INVALID); L < win_length, reflect padding with L <= win_length / 2, B > 65535 or B T F >= 2^31 (SF_ERR_SHAPE); a
+ * workspace below the query (SF_ERR_WORKSPACE).  A row's results do not depend on the rest of the batch (fixed-order sums, no atomics). */
+typedef struct sf_spectral_gate_handle sf_spectral_gate_handle;
+int sf_spectral_gate_create(int n_fft, int win_length, int hop, int center, int pad_mode, int scale_spectrum, const float *freq_taps /*host*/,
+                            int n_freq_taps, const float *time_taps /*host*/, int n_time_taps, sf_spectral_gate_handle **out);
+void sf_spectral_gate_destroy(sf_spectral_gate_handle *h);
+int sf_spectral_gate_frames(const sf_spectral_gate_handle *h, int L);
+int64_t sf_spectral_gate_workspace_bytes(const sf_spectral_gate_handle *h, int B, int L);
+int sf_stft_forward(sf_spectral_gate_handle *h, const float *wav, int B, int L, float *spec, void *stream);
+int sf_istft_forward(sf_spectral_gate_handle *h, const float *spec, int B, int T, float *out, int out_len, void *ws, int64_t ws_bytes, void *stream);
+int sf_spectral_gate_noise_threshold(sf_spectral_gate_handle *h, const float *noise, int B, int L, float n_std, float *thresh, void *ws,
+                                     int64_t ws_bytes, void *stream);
+int sf_spectral_gate(sf_spectral_gate_handle *h, const float *wav, int B, int L, int stationary, float smooth_b, float thresh_mult, float slope,
+                     float prop_decrease, int prop_before_smoothing, const float *thresh, float *spec, float *mask_raw, float *mask_smooth, float *out, void *ws,
+                     int64_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * FAD evaluation (syncfusion_amd/fad.py)
  *   replaces: main.evaluation.evaluate_fad (main/evaluation.py:7-28, the config.evaluation target of script/evaluate_diffusion.py:31-36):
  *   frechet_audio_distance.FrechetAudioDistance(model_name="vggish", use_pca=False, use_activation=False) -- the VGGish input features

@@ -6,10 +6,11 @@ Public surface = the reference's own: ``DiffusionModel`` 
 runs in ``lib/libsyncfusion_amd.so`` (hand-written HIP, C ABI in include/syncfusion_amd.h).
 """
 from . import _lib  # noqa: F401
-from . import audio_features, autograd, clap, clap_text, evaluation, fad, frame_transforms, jpeg, onset_test, onset_training, shards, training, video_chunks  # noqa: F401
+from . import audio_features, autograd, clap, clap_text, denoise, evaluation, fad, frame_transforms, jpeg, onset_test, onset_training, shards, training, video_chunks  # noqa: F401
 from .config import instantiate, instantiate_class, instantiate_frames_transforms, instantiate_model_yaml
 from .diffusion import DiffusionModel, LinearSchedule, UNetV0, VDiffusion, VInpainter, VSampler
 from .audio_features import MelSpectrogram, mel_filterbank, onset_detect, onset_strength
+from .denoise import SpectralGateConfig, chunk_rows, istft, merge_rows, reduce_noise, stft
 from .encoder1d import Encoder1d
 from .evaluation import evaluate_onsets
 from .clap import ClapAudioConfig, ClapAudioEmbedder
@@ -36,5 +37,6 @@ __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule
            "VInpainter", "inpaint_batch", "generate_long", "long_windows", "regions_to_keep_mask",
            "onset_test", "OnsetTestStage", "annotation_rows", "pack_onset_preds", "test_onset_model", "prepare_gt_for_fad",
            "jpeg", "JpegInfo", "decode_jpeg_batch", "parse_jpeg", "run_onset_test",
-           "clap", "ClapAudioConfig", "ClapAudioEmbedder", "clap_text", "ClapEmbedder", "ClapTextConfig", "ClapTokenizer"]
+           "clap", "ClapAudioConfig", "ClapAudioEmbedder", "clap_text", "ClapEmbedder", "ClapTextConfig", "ClapTokenizer",
+           "denoise", "SpectralGateConfig", "reduce_noise", "stft", "istft", "chunk_rows", "merge_rows"]
 __version__ = "0.1.0"

@@ -261,6 +261,20 @@ SYMBOLS = {
     # (h, wav, B, L, amin, top_db, lag, pre_max, post_max, pre_avg, post_avg, wait, delta, conf_interval, capacity, envelope, count, positions,
     #  confidence, strength, ws, ws_bytes, stream)
     "sf_onset_detect": (_I, [_P, _P, _I, _I, _F, _F, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
+    # the STFT pair and the spectral-gating denoiser (syncfusion_amd/denoise.py)
+    # (n_fft, win_length, hop, center, pad_mode, scale_spectrum, freq_taps_host, n_freq_taps, time_taps_host, n_time_taps, out)
+    "sf_spectral_gate_create": (_I, [_I, _I, _I, _I, _I, _I, _P, _I, _P, _I, C.POINTER(_P)]),
+    "sf_spectral_gate_destroy": (None, [_P]),
+    "sf_spectral_gate_frames": (_I, [_P, _I]),
+    "sf_spectral_gate_workspace_bytes": (_L, [_P, _I, _I]),
+    # (h, wav, B, L, spec, stream)
+    "sf_stft_forward": (_I, [_P, _P, _I, _I, _P, _P]),
+    # (h, spec, B, T, out, out_len, ws, ws_bytes, stream)
+    "sf_istft_forward": (_I, [_P, _P, _I, _I, _P, _I, _P, _L, _P]),
+    # (h, noise, B, L, n_std, thresh, ws, ws_bytes, stream)
+    "sf_spectral_gate_noise_threshold": (_I, [_P, _P, _I, _I, _F, _P, _P, _L, _P]),
+    # (h, wav, B, L, stationary, smooth_b, thresh_mult, slope, prop_decrease, prop_before_smoothing, thresh, spec, mask_raw, mask_smooth, out, ws, ws_bytes, stream)
+    "sf_spectral_gate": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
     # the FAD evaluation (syncfusion_amd/fad.py)
     # (n_fft, win_length, hop, n_mels, first_bin_host, bin_count_host, weights_host, n_weights, out)
     "sf_audio_features_create_framed": (_I, [_I, _I, _I, _I, _P, _P, _P, _L, C.POINTER(_P)]),

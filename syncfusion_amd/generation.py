@@ -194,6 +194,21 @@ def save_wav(path: Union[str, Path], audio: Tensor, sample_rate: int) -> None:
         f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
+def save_wav_pcm16(path: Union[str, Path], audio: Tensor, sample_rate: int) -> None:
+    """(channels, n) float tensor -> 16-bit PCM wav (format tag 1), the file ``torchaudio.save(..., bits_per_sample=16)`` writes for a float
+    tensor: samples are scaled by 32768, rounded to nearest and clamped to [-32768, 32767].  ``load_wav`` reads it back."""
+    a = audio.detach().to(torch.float32).cpu()
+    if a.dim() != 2:
+        raise ValueError(f"save_wav_pcm16 expects (channels, samples), got shape {tuple(a.shape)}")
+    ch = int(a.shape[0])
+    data = torch.clamp(torch.round(a.t().contiguous() * 32768.0), -32768.0, 32767.0).to(torch.int16).numpy().astype("<i2", copy=False).tobytes()
+    rate = int(sample_rate)
+    fmt = struct.pack("<HHIIHH", 1, ch, rate, rate * ch * 2, ch * 2, 16)
+    body = b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt + b"data" + struct.pack("<I", len(data)) + data
+    with open(str(path), "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+
+
 def load_wav(path: Union[str, Path]):
     """Reader for the files ``save_wav`` writes (and 16-bit PCM wav): -> ((channels, n) float32 tensor, sample_rate).
     The standard library's ``wave`` module rejects format tag 3."""
