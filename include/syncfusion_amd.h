@@ -137,6 +137,18 @@ int sf_vinpaint(sf_unet *h, float *x_inout, const float *source, const uint8_t *
                 int L0, int num_steps, int num_resamples, uint64_t seed, float embedding_scale, int use_graph, void *ws, int64_t ws_bytes,
                 void *stream);
 
+/* The sampling loop with a linear multistep rule on x0_hat = alpha x - beta v and a caller-given schedule, in place ("Multistep
+ * sampler"; an addition, not part of the reference):  step i evaluates v at sigmas[i] and applies
+ *   X_i = al x - be v,   x <- cx x + c0 X_i + c1 X_{i-1},      (al, be, cx, c0, c1) = table[8 i .. 8 i + 4]   (X_{-1} = 0)
+ *   sigmas: HOST, num_steps + 1 floats, finite, strictly decreasing, inside [0, 1].  table: HOST, num_steps rows of 8 floats (three unused),
+ *   finite; syncfusion_amd.solvers.solver_table builds it.  Both are copied into the workspace before the call returns.
+ *   Conditioning, graph use and the single host synchronisation are sf_vsample's; the step graph is cached separately from sf_vsample's and
+ *   sf_vinpaint's and replayed for any later table / sigmas of the same shape, workspace and guidance scale.
+ *   The workspace is larger than sf_vsample's (the history X_{i-1} and the table live in it): sf_vsample_ms_workspace_bytes. */
+int64_t sf_vsample_ms_workspace_bytes(const sf_unet *h, int B, int L0, int two_pass, int num_steps);
+int sf_vsample_ms(sf_unet *h, float *x_inout, const float *const *ctx, const float *emb, int B, int L0, int num_steps, float embedding_scale,
+                  const float *sigmas, const float *table, int use_graph, void *ws, int64_t ws_bytes, void *stream);
+
 /* Debug taps (tests only): after the next sf_unet_forward, every block-level activation is
  * copied as fp32 channels-last rows into `buf` (device).  Query the table afterwards. */
 int sf_unet_debug_enable(sf_unet *h, float *buf, int64_t cap_floats);
@@ -303,6 +315,12 @@ int sf_op_philox_normal(uint64_t seed, uint32_t k, int64_t elem_offset, int64_t 
  * the alignment of the pointers (16-byte accesses only where every base allows them). */
 int sf_op_vinpaint_update(float *x, const float *v, const float *v_uncond, float scale, const float *source, const uint8_t *mask,
                           const float *sched, const int32_t *step_idx, const uint32_t *seed, int64_t e0, int64_t e1, void *stream);
+/* One launch of the multistep sampler's update on the elements [e0, e1) of whole tensors (every pointer is the base of the WHOLE tensor; device
+ * memory): with k = *step_idx and (al, be, cx, c0, c1) = table[8k .. 8k+4] (rows of 8 floats, three unused),
+ *   X = al x - be v,   x[e] <- cx x + c0 X + c1 hist[e],   hist[e] <- X,        v = v_uncond ? v_u + (v - v_u) * scale : v
+ * The result of an element does not depend on how [0, n) is cut into ranges, nor on the alignment of the pointers. */
+int sf_op_vsampler_update_ms(float *x, const float *v, const float *v_uncond, float scale, float *hist, const float *table,
+                             const int32_t *step_idx, int64_t e0, int64_t e1, void *stream);
 /* out = conv1d(silu(groupnorm(x))) + bias (+ residual).  x:(B,L,C) and out/residual:(B,Lout,N) channels-last in
  * `dtype`; w:(N,C,taps) fp32 in PyTorch layout (packed internally); groups==0 -> no norm/activation;
  * upsample = nearest-neighbour factor applied before the convolution.  Lout = (L*upsample + 2*pad - taps)/stride + 1. */

@@ -8,7 +8,8 @@ runs in ``lib/libsyncfusion_amd.so`` (hand-written HIP, C ABI in include/syncfus
 from . import _lib  # noqa: F401
 from . import audio_features, autograd, clap, clap_text, denoise, evaluation, fad, frame_transforms, jpeg, onset_test, onset_training, shards, training, video_chunks  # noqa: F401
 from .config import instantiate, instantiate_class, instantiate_frames_transforms, instantiate_model_yaml
-from .diffusion import DiffusionModel, LinearSchedule, UNetV0, VDiffusion, VInpainter, VSampler
+from .diffusion import DiffusionModel, LinearSchedule, PowerSchedule, UNetV0, VDiffusion, VInpainter, VSampler
+from .solvers import solver_table
 from .audio_features import MelSpectrogram, mel_filterbank, onset_detect, onset_strength
 from .denoise import SpectralGateConfig, chunk_rows, istft, merge_rows, reduce_noise, stft
 from .encoder1d import Encoder1d
@@ -18,7 +19,7 @@ from .clap_text import ClapEmbedder, ClapTextConfig, ClapTokenizer
 from .fad import VGGish, VGGishConfig, embedding_statistics, evaluate_fad, frechet_distance
 from .jpeg import JpegInfo, decode_jpeg_batch, parse_jpeg
 from .generation import (generate_batch, generate_dataset, generate_long, inpaint_batch, long_windows, prepare_gt_for_fad,
-                         regions_to_keep_mask)
+                         regions_to_keep_mask, vary_batch)
 from .module import Model, RandomEmbedder
 from .module_onset import Model as OnsetModel
 from .onset_net import VideoOnsetNet
@@ -38,5 +39,6 @@ __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule
            "onset_test", "OnsetTestStage", "annotation_rows", "pack_onset_preds", "test_onset_model", "prepare_gt_for_fad",
            "jpeg", "JpegInfo", "decode_jpeg_batch", "parse_jpeg", "run_onset_test",
            "clap", "ClapAudioConfig", "ClapAudioEmbedder", "clap_text", "ClapEmbedder", "ClapTextConfig", "ClapTokenizer",
-           "denoise", "SpectralGateConfig", "reduce_noise", "stft", "istft", "chunk_rows", "merge_rows"]
+           "denoise", "SpectralGateConfig", "reduce_noise", "stft", "istft", "chunk_rows", "merge_rows",
+           "solver_table", "PowerSchedule", "vary_batch"]
 __version__ = "0.1.0"

@@ -209,6 +209,35 @@ class UNetEngine(_Base):
                                       _lib.stream_ptr(self.device)), "sf_vsample")
         return x
 
+    def sample_ms(self, x_noisy: torch.Tensor, sigmas, table, channels: Sequence[torch.Tensor], embedding: torch.Tensor,
+                  embedding_scale: float = 1.0, use_graph: bool = True) -> torch.Tensor:
+        """The multistep loop inside ``sf_vsample_ms``.  ``sigmas``: ``T + 1`` host floats; ``table``: ``(T, 8)`` host fp32 rows
+        (``syncfusion_amd.solvers.pack_table``).  ``x_noisy`` is left untouched."""
+        import numpy as np
+
+        _lib.require_gpu_tensor(x_noisy, "DiffusionModel.sample")
+        self._check_inputs(x_noisy, channels, embedding)
+        sig = np.ascontiguousarray(sigmas, dtype=np.float32)
+        tab = np.ascontiguousarray(table, dtype=np.float32)
+        num_steps = sig.size - 1
+        if sig.ndim != 1 or num_steps < 1 or tab.shape != (num_steps, 8):
+            raise ValueError(f"expected T + 1 sigmas and a (T, 8) table, got shapes {sig.shape} and {tab.shape}")
+        B, _, L0 = x_noisy.shape
+        with torch.cuda.device(self.device):
+            x = _lib.f32c(x_noisy).clone()
+            ctx = [_lib.f32c(c) for c in channels]
+            emb = _lib.f32c(embedding)
+            two = float(embedding_scale) != 1.0
+            # sized for at least 256 steps, as sample()'s: a later call with more finds the same buffer and the cached step graph
+            n = self.lib.sf_vsample_ms_workspace_bytes(self.handle, B, L0, int(two), max(num_steps, 256))
+            if n < 0:
+                raise _lib.SyncFusionAmdError(f"unsupported shape B={B}, L0={L0}: {self.lib.sf_last_error().decode()}")
+            ws = self._workspace(n, self.device)
+            check(self.lib.sf_vsample_ms(self.handle, x.data_ptr(), _lib.ptr_array(ctx), emb.data_ptr(), B, L0, num_steps, float(embedding_scale),
+                                         sig.ctypes.data, tab.ctypes.data, int(bool(use_graph)), ws.data_ptr(), ws.numel(),
+                                         _lib.stream_ptr(self.device)), "sf_vsample_ms")
+        return x
+
     def inpaint(self, source: torch.Tensor, mask: torch.Tensor, num_steps: int, num_resamples: int, channels: Sequence[torch.Tensor],
                 embedding: torch.Tensor, embedding_scale: float = 1.0, x_noisy: Optional[torch.Tensor] = None, seed: int = 0,
                 use_graph: bool = True) -> torch.Tensor:

@@ -113,6 +113,11 @@ SYMBOLS = {
     "sf_vsample": (_I, [_P, _P, C.POINTER(_P), _P, _I, _I, _I, _F, _I, _P, _L, _P]),
     "sf_vinpaint_workspace_bytes": (_L, [_P, _I, _I, _I, _I, _I]),
     "sf_vinpaint": (_I, [_P, _P, _P, _P, C.POINTER(_P), _P, _I, _I, _I, _I, C.c_uint64, _F, _I, _P, _L, _P]),
+    "sf_vsample_ms_workspace_bytes": (_L, [_P, _I, _I, _I, _I]),
+    # (h, x_inout, ctx, emb, B, L0, num_steps, embedding_scale, sigmas_host, table_host, use_graph, ws, ws_bytes, stream)
+    "sf_vsample_ms": (_I, [_P, _P, C.POINTER(_P), _P, _I, _I, _I, _F, _P, _P, _I, _P, _L, _P]),
+    # (x, v, v_uncond, scale, hist, table, step_idx, e0, e1, stream)
+    "sf_op_vsampler_update_ms": (_I, [_P, _P, _P, _F, _P, _P, _P, _L, _L, _P]),
     "sf_op_philox_normal": (_I, [C.c_uint64, C.c_uint32, _L, _L, _P, _P]),
     "sf_op_vinpaint_update": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _L, _L, _P]),
     "sf_unet_debug_enable": (_I, [_P, _P, _L]),

@@ -141,6 +141,15 @@ int sf_op_vinpaint_update(float *x, const float *v, const float *v_uncond, float
   SF_API_END
 }
 
+int sf_op_vsampler_update_ms(float *x, const float *v, const float *v_uncond, float scale, float *hist, const float *table, const int32_t *step_idx,
+                             int64_t e0, int64_t e1, void *stream) {
+  SF_API_BEGIN
+  if (!x || !v || !hist || !table || !step_idx || e0 < 0 || e1 < e0) fail(SF_ERR_INVALID, "bad argument");
+  SF_HIP(launch_vsampler_update_ms(x, v, v_uncond, scale, hist, table, step_idx, 0, e0, e1, static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
 int sf_cut_prefix_crop(const float *gen, const float *y, int B, int C, int L, int cut_length, float *out, int32_t *first_onset, void *stream) {
   SF_API_BEGIN
   if (!gen || !y || !out || !first_onset || B < 1 || C < 1 || L < 1 || cut_length < 1 || cut_length > L) fail(SF_ERR_INVALID, "bad argument");

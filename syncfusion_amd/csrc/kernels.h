@@ -377,6 +377,11 @@ hipError_t launch_vsampler_update(float *x, const float *v, const float *v_uncon
 hipError_t launch_vinpaint_update(float *x, const float *v, const float *v_uncond, float scale, const float *source, const uint8_t *mask,
                                   const float *sched, const int *step_idx, int step_bias, const uint32_t *seed, int64_t e0, int64_t e1,
                                   hipStream_t s);
+// Linear multistep v-sampler step (sampler.hip), in place on x and hist, for the elements [e0, e1) of the whole tensor (range convention of
+// launch_vinpaint_update):  X = al*x - be*v,  x <- cx*x + c0*X + c1*hist,  hist <- X,  v as in the v-sampler step above,
+//   (al, be, cx, c0, c1) = table[8k .. 8k+4],  k = *step_idx + step_bias  (rows of 8 floats, three unused).
+hipError_t launch_vsampler_update_ms(float *x, const float *v, const float *v_uncond, float scale, float *hist, const float *table,
+                                     const int *step_idx, int step_bias, int64_t e0, int64_t e1, hipStream_t s);
 // out[i] = standard normal of element (elem_offset + i) at virtual iteration k: Philox4x32-10 with counter (g lo, g hi, k, 0), g = element >> 2,
 // key (seed lo, seed hi), Box-Muller on u(w) = ((w >> 9) + 0.5) * 2^-23; lane = element & 3 ("Inpainting sampler")
 hipError_t launch_philox_normal(uint64_t seed, uint32_t k, int64_t elem_offset, int64_t n, float *out, hipStream_t s);

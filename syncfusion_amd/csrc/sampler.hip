@@ -1,5 +1,6 @@
 // Inpainting sampler kernels: counter-based device noise (Philox4x32-10 + Box-Muller) and the fused VInpainter update
-// (v-sampler step + re-noised source blend).  HBM-bound streaming, one Philox group (four consecutive elements) per thread.
+// (v-sampler step + re-noised source blend); the linear multistep update of sf_vsample_ms.  HBM-bound streaming, one Philox group (four
+// consecutive elements) per thread.
 #include "common.h"
 #include "kernels.h"
 
@@ -163,7 +164,83 @@ __global__ void vinpaint_update_kernel(float *__restrict__ x, const float *__res
   }
 }
 
+// One element of the multistep update with its roundings spelled out (the 16-byte path and the element-wise ends must agree bit for bit):
+//   X = fma(al, x, -(be * v)),  x <- fma(c1, hist, fma(c0, X, cx * x)),  hist <- X
+__device__ __forceinline__ float ms_x0(float xx, float vv, float al, float be) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(al, xx, -(be * vv));
+}
+__device__ __forceinline__ float ms_next(float xx, float X, float hh, float cx, float c0, float c1) {
+#pragma clang fp contract(off)
+  const float p = cx * xx;
+  return __builtin_fmaf(c1, hh, __builtin_fmaf(c0, X, p));
+}
+
+// Linear multistep step of the v-sampler ("Multistep sampler"), in place on x and on the history, for the elements [e0, e1) of the
+// whole tensor (range convention of vinpaint_update_kernel: every pointer is the base of the WHOLE tensor, a branch passes its slice as the range):
+//   X = al * x - be * v,   x <- cx * x + c0 * X + c1 * hist,   hist <- X,    (al, be, cx, c0, c1) = table[8 k .. 8 k + 4],  k = *step_idx + step_bias
+// The row is 8 floats (three unused) at a 32-byte aligned address that is the same for every lane: one scalar load.  Nothing that changes
+// between calls is an argument (graph replay): the coefficients are read from device memory.
+__global__ void vsampler_update_ms_kernel(float *__restrict__ x, const float *__restrict__ v, const float *__restrict__ vu, float scale,
+                                          float *__restrict__ hist, const float *__restrict__ table, const int *__restrict__ step_idx, int step_bias,
+                                          int64_t e0, int64_t e1, int vec) {
+  const int k = *step_idx + step_bias;
+  const float *row = table + 8 * (int64_t)k;
+  const float al = row[0], be = row[1], cx = row[2], c0 = row[3], c1 = row[4];
+  const int64_t g_lo = e0 >> 2, ng = ((e1 + 3) >> 2) - g_lo;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < ng; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = 4 * (g_lo + t);
+    if (vec && e >= e0 && e + 4 <= e1) {
+      const float4 xx = *reinterpret_cast<const float4 *>(x + e);
+      const float4 hh = *reinterpret_cast<const float4 *>(hist + e);
+      float4 vv = *reinterpret_cast<const float4 *>(v + e);
+      if (vu) {
+        const float4 m = *reinterpret_cast<const float4 *>(vu + e);
+        vv.x = guide(vv.x, m.x, scale);
+        vv.y = guide(vv.y, m.y, scale);
+        vv.z = guide(vv.z, m.z, scale);
+        vv.w = guide(vv.w, m.w, scale);
+      }
+      float4 X, o;
+      X.x = ms_x0(xx.x, vv.x, al, be);
+      X.y = ms_x0(xx.y, vv.y, al, be);
+      X.z = ms_x0(xx.z, vv.z, al, be);
+      X.w = ms_x0(xx.w, vv.w, al, be);
+      o.x = ms_next(xx.x, X.x, hh.x, cx, c0, c1);
+      o.y = ms_next(xx.y, X.y, hh.y, cx, c0, c1);
+      o.z = ms_next(xx.z, X.z, hh.z, cx, c0, c1);
+      o.w = ms_next(xx.w, X.w, hh.w, cx, c0, c1);
+      *reinterpret_cast<float4 *>(x + e) = o;
+      *reinterpret_cast<float4 *>(hist + e) = X;
+    } else {
+      for (int l = 0; l < 4; ++l) {
+        const int64_t i = e + l;
+        if (i < e0 || i >= e1) continue;
+        float vv = v[i];
+        if (vu) {
+          const float m = vu[i];
+          vv = guide(vv, m, scale);
+        }
+        const float xx = x[i];
+        const float X = ms_x0(xx, vv, al, be);
+        x[i] = ms_next(xx, X, hist[i], cx, c0, c1);
+        hist[i] = X;
+      }
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t launch_vsampler_update_ms(float *x, const float *v, const float *v_uncond, float scale, float *hist, const float *table,
+                                     const int *step_idx, int step_bias, int64_t e0, int64_t e1, hipStream_t s) {
+  if (e1 <= e0) return hipSuccess;
+  auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const int vec = al16(x) && al16(v) && (!v_uncond || al16(v_uncond)) && al16(hist);
+  hipLaunchKernelGGL(vsampler_update_ms_kernel, grid_for((e1 - e0 + 3) / 4 + 1), dim3(TPB), 0, s, x, v, v_uncond, scale, hist, table, step_idx,
+                     step_bias, e0, e1, vec);
+  return hipGetLastError();
+}
 
 hipError_t launch_philox_normal(uint64_t seed, uint32_t k, int64_t elem_offset, int64_t n, float *out, hipStream_t s) {
   if (n <= 0) return hipSuccess;

@@ -85,6 +85,9 @@ struct Plan {  // everything carved out of the caller's workspace for one (B, L0
   float *src = nullptr;
   uint8_t *mask = nullptr;
   uint32_t *seed = nullptr;
+  // multistep loop only (sf_vsample_ms): X_{i-1} of every element and the coefficient table [steps][8] the update kernel reads
+  float *hist = nullptr;
+  float *table = nullptr;
 };
 
 }  // namespace
@@ -142,10 +145,11 @@ struct sf_unet {
     int B = 0, L0 = 0, T = 0, nbr = 0;
     bool two = false, valid = false;
     bool inpaint = false;   // sf_vinpaint's step (other update kernel, other workspace layout) never replays sf_vsample's, nor the reverse
+    bool multistep = false; // nor does sf_vsample_ms's step replay as either of them, nor they as it
     float scale = 0.f;
     const void *ws = nullptr;
     bool operator==(const GraphKey &o) const {
-      return valid && o.valid && inpaint == o.inpaint && B == o.B && L0 == o.L0 && T == o.T && nbr == o.nbr && two == o.two && scale == o.scale && ws == o.ws;
+      return valid && o.valid && inpaint == o.inpaint && multistep == o.multistep && B == o.B && L0 == o.L0 && T == o.T && nbr == o.nbr && two == o.two && scale == o.scale && ws == o.ws;
     }
   } gkey;
   // Step graphs of OTHER recently used (shape, workspace, guidance) combinations: a server alternating between a few request
@@ -611,7 +615,7 @@ void build(sf_unet &u, const WeightMap *wm, hipStream_t s) {
 constexpr int kSchedSteps = 1024;   // schedule capacity that keeps the workspace layout independent of num_steps
 constexpr int64_t kMaxVirtualSteps = 1 << 24;   // sf_vinpaint: num_steps * num_resamples (an int row count everywhere below)
 
-Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num_steps, bool inpaint = false) {
+Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num_steps, bool inpaint = false, bool multistep = false) {
   const sf_unet_config &c = u.cfg;
   Plan p;
   p.B = B;
@@ -756,10 +760,16 @@ Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num
     p.mask = ws.alloc_n<uint8_t>(n);
     p.seed = ws.alloc_n<uint32_t>(4);
   }
+  const int64_t ns = std::max<int64_t>(num_steps > 0 ? num_steps : 1, kSchedSteps);
+  // The multistep loop's own buffers, likewise only in ITS layout: the history X_{i-1} and the coefficient table (rows of 8 floats; fixed
+  // capacity up to kSchedSteps steps, like the schedule below).
+  if (multistep) {
+    p.hist = ws.alloc_n<float>((int64_t)B * L0 * c.in_channels);
+    p.table = ws.alloc_n<float>(8 * ns);
+  }
   // Everything whose SIZE depends on the number of steps comes last, so that no other address does: a step graph
   // instantiated for one num_steps stays valid for another (up to kSchedSteps; the tables are indexed by the device
   // step counter).  Order: step counter, schedule (fixed capacity), sigmas, modulation table, time-MLP rows.
-  const int64_t ns = std::max<int64_t>(num_steps > 0 ? num_steps : 1, kSchedSteps);
   p.step = ws.alloc_n<int>(16);   // device step counters: one per independent branch pipeline
   p.sched = ws.alloc_n<float>(4 * ns);
   p.sigs = ws.alloc_n<float>(ns + p.Bt);
@@ -1703,10 +1713,10 @@ struct Exec {
   }
 };
 
-void check_ws(const sf_unet *h, void *ws, int64_t ws_bytes, int B, int L0, bool two, int steps, bool inpaint = false) {
+void check_ws(const sf_unet *h, void *ws, int64_t ws_bytes, int B, int L0, bool two, int steps, bool inpaint = false, bool multistep = false) {
   if (!ws) fail(SF_ERR_WORKSPACE, "workspace is null");
   Workspace dry(nullptr, 0);
-  make_plan(*h, dry, B, L0, two, steps, inpaint);
+  make_plan(*h, dry, B, L0, two, steps, inpaint, multistep);
   if (dry.used() > ws_bytes) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes, have %lld", (long long)dry.used(), (long long)ws_bytes);
 }
 
@@ -1821,25 +1831,30 @@ int sf_unet_forward(sf_unet *h, const float *x, const float *sigma, const float 
   SF_API_END
 }
 
-// The sampling loop behind sf_vsample and sf_vinpaint.  `inp` == nullptr: VSampler, num_steps steps.  Otherwise VInpainter: the same loop over
-// num_steps * num_resamples virtual steps -- virtual step k = i * R + r has the schedule row (alpha_i, beta_i, alpha_{i+j}, beta_{i+j}),
-// j = (r == R - 1), and sigma_i -- whose update launch also blends the re-noised source in where the mask is set.
+// The sampling loop behind sf_vsample, sf_vinpaint and sf_vsample_ms.  `inp` == nullptr: VSampler, num_steps steps.  Otherwise VInpainter: the same
+// loop over num_steps * num_resamples virtual steps -- virtual step k = i * R + r has the schedule row (alpha_i, beta_i, alpha_{i+j}, beta_{i+j}),
+// j = (r == R - 1), and sigma_i -- whose update launch also blends the re-noised source in where the mask is set.  `ms` != nullptr (never with
+// `inp`): the caller's sigmas instead of the built-in schedule, and the multistep update launch with its coefficient table and history.
 struct InpaintArgs {
   const float *source;
   const uint8_t *mask;
   int num_resamples;
   uint64_t seed;
 };
+struct MultistepArgs {
+  const float *sigmas;   // host, num_steps + 1
+  const float *table;    // host, num_steps rows of 8
+};
 
 static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const float *const *ctx, const float *emb, int B, int L0, int num_steps,
-                        float embedding_scale, int use_graph, void *ws, int64_t ws_bytes, void *stream) {
-  const char *const tag = inp ? "sf_vinpaint" : "sf_vsample";
+                        float embedding_scale, int use_graph, void *ws, int64_t ws_bytes, void *stream, const MultistepArgs *ms = nullptr) {
+  const char *const tag = inp ? "sf_vinpaint" : (ms ? "sf_vsample_ms" : "sf_vsample");
   const int R = inp ? inp->num_resamples : 1;
   const int T = num_steps * R;   // (virtual) steps of the loop
   const bool two = embedding_scale != 1.0f;
-  check_ws(h, ws, ws_bytes, B, L0, two, T, inp != nullptr);
+  check_ws(h, ws, ws_bytes, B, L0, two, T, inp != nullptr, ms != nullptr);
   Workspace w(ws, ws_bytes);
-  Plan p = make_plan(*h, w, B, L0, two, T, inp != nullptr);
+  Plan p = make_plan(*h, w, B, L0, two, T, inp != nullptr, ms != nullptr);
   hipStream_t user = static_cast<hipStream_t>(stream);
   hipStream_t s = user;
   if (use_graph && T > 1) {
@@ -1889,7 +1904,9 @@ static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const floa
   // (torch.linspace: start + i*step for the first half, end - (steps-1-i)*step for the second).
   const int S = num_steps;
   std::vector<float> sig(S + 1), host(4 * (size_t)T + (size_t)T);
-  {
+  if (ms) {
+    for (int i = 0; i <= S; ++i) sig[i] = ms->sigmas[i];
+  } else {
     const float step = (0.0f - 1.0f) / (float)S;
     const int halfway = (S + 1) / 2;
     for (int i = 0; i <= S; ++i) sig[i] = (i < halfway) ? (1.0f + step * (float)i) : (0.0f - step * (float)(S - i));
@@ -1919,6 +1936,12 @@ static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const floa
     SF_HIP(hipMemcpyAsync(p.mask, inp->mask, n, hipMemcpyDeviceToDevice, s));
     SF_HIP(hipMemcpyAsync(p.seed, seed_words, sizeof(seed_words), hipMemcpyHostToDevice, s));
   }
+  // Likewise the multistep table (the caller's array outlives the copy: the synchronisation below).  The history is zeroed: row 0 has
+  // c1 == 0, but 0 * (whatever the workspace held) may be NaN.
+  if (ms) {
+    SF_HIP(hipMemcpyAsync(p.table, ms->table, 8 * (size_t)T * sizeof(float), hipMemcpyHostToDevice, s));
+    SF_HIP(hipMemsetAsync(p.hist, 0, n * sizeof(float), s));
+  }
   // sigma_i is the same for every clip, so the time MLP and the 42 Modulation / SkipModulate projections of ALL steps
   // are one set of GEMMs with M = num_steps, once per call (instead of five launches inside every step); a step then
   // starts by selecting its row (which also advances the device step counter) and every consumer reads that one row
@@ -1935,6 +1958,8 @@ static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const floa
     const float *vu = two ? p.vout + n : nullptr;
     if (inp)
       SF_HIP(launch_vinpaint_update(xs, p.vout, vu, embedding_scale, p.src, p.mask, sched, counter, ahead ? -1 : 0, p.seed, e0, e1, su));
+    else if (ms)
+      SF_HIP(launch_vsampler_update_ms(xs, p.vout, vu, embedding_scale, p.hist, p.table, counter, ahead ? -1 : 0, e0, e1, su));
     else
       SF_HIP(launch_vsampler_update(xs + e0, p.vout + e0, vu ? vu + e0 : nullptr, embedding_scale, ahead ? sched - 4 : sched, counter, e1 - e0, su));
   };
@@ -1957,6 +1982,7 @@ static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const floa
   key.nbr = p.nbr;
   key.two = two;
   key.inpaint = inp != nullptr;
+  key.multistep = ms != nullptr;
   key.scale = embedding_scale;
   key.ws = ws;
   key.valid = true;
@@ -2096,6 +2122,36 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
   if (!emb) fail(SF_ERR_INVALID, "ClassifierFreeGuidancePlugin requires embedding");
   if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
   run_sampler(h, x, nullptr, ctx, emb, B, L0, num_steps, embedding_scale, use_graph, ws, ws_bytes, stream);
+  return SF_OK;
+  SF_API_END
+}
+
+int64_t sf_vsample_ms_workspace_bytes(const sf_unet *h, int B, int L0, int two_pass, int num_steps) {
+  try {
+    if (!h) fail(SF_ERR_INVALID, "null handle");
+    if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
+    Workspace dry(nullptr, 0);
+    make_plan(*h, dry, B, L0, two_pass != 0, num_steps, false, true);
+    return dry.used();
+  } catch (const EngineError &) {
+    return -1;
+  }
+}
+
+int sf_vsample_ms(sf_unet *h, float *x, const float *const *ctx, const float *emb, int B, int L0, int num_steps, float embedding_scale,
+                  const float *sigmas, const float *table, int use_graph, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!h || !x || !ctx || !sigmas || !table) fail(SF_ERR_INVALID, "null argument");
+  if (!emb) fail(SF_ERR_INVALID, "ClassifierFreeGuidancePlugin requires embedding");
+  if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
+  for (int i = 0; i <= num_steps; ++i) {
+    if (!(sigmas[i] >= 0.0f && sigmas[i] <= 1.0f)) fail(SF_ERR_INVALID, "sigmas[%d] = %g is not inside [0, 1]", i, (double)sigmas[i]);
+    if (i > 0 && !(sigmas[i] < sigmas[i - 1])) fail(SF_ERR_INVALID, "sigmas must be strictly decreasing (at %d)", i);
+  }
+  for (int64_t i = 0; i < 8 * (int64_t)num_steps; ++i)
+    if (!std::isfinite(table[i])) fail(SF_ERR_INVALID, "solver table entry %lld is not finite", (long long)i);
+  const MultistepArgs ms{sigmas, table};
+  run_sampler(h, x, nullptr, ctx, emb, B, L0, num_steps, embedding_scale, use_graph, ws, ws_bytes, stream, &ms);
   return SF_OK;
   SF_API_END
 }

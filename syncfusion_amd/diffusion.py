@@ -238,12 +238,29 @@ class UNetV0(nn.Module):
 
 
 class LinearSchedule(nn.Module):
+    """``num_steps`` sigmas from ``start`` down to ``end``, evenly spaced; any ``1 >= start > end >= 0``."""
+
     def __init__(self, start: float = 1.0, end: float = 0.0):
         super().__init__()
         self.start, self.end = start, end
 
     def forward(self, num_steps: int, device=None) -> Tensor:
         return torch.linspace(self.start, self.end, num_steps, device=device)
+
+
+class PowerSchedule(nn.Module):
+    """``sigma_i = end + (start - end) * (1 - i / T) ** rho`` for ``i = 0 .. T = num_steps - 1``: denser near ``end`` for ``rho > 1``
+    (``rho = 1`` is ``LinearSchedule``'s spacing).  An addition, not part of audio_diffusion_pytorch."""
+
+    def __init__(self, start: float = 1.0, end: float = 0.0, rho: float = 2.0):
+        super().__init__()
+        if not rho > 0:
+            raise ValueError(f"rho must be positive, got {rho}")
+        self.start, self.end, self.rho = start, end, rho
+
+    def forward(self, num_steps: int, device=None) -> Tensor:
+        u = 1.0 - torch.arange(num_steps, dtype=torch.float64) / max(num_steps - 1, 1)
+        return (self.end + (self.start - self.end) * u ** self.rho).to(dtype=torch.float32, device=device)
 
 
 class VDiffusion(nn.Module):
@@ -274,16 +291,32 @@ class VDiffusion(nn.Module):
         return self.loss_fn(v_pred, v_target)
 
 
+def _is_default_schedule(schedule) -> bool:
+    return type(schedule) is LinearSchedule and (schedule.start, schedule.end) == (1.0, 0.0)
+
+
 class VSampler(nn.Module):
-    """Deterministic DDIM-style sampler in v-space; the whole loop runs inside ``sf_vsample``."""
+    """Deterministic sampler in v-space; the whole loop runs on the device.
+
+    ``solver="ddim"`` with ``LinearSchedule(1, 0)`` (the defaults) is audio_diffusion_pytorch's ``VSampler`` and runs inside ``sf_vsample``.
+    Any other combination runs inside ``sf_vsample_ms``: ``solver`` is one of ``syncfusion_amd.solvers.SOLVERS`` (``"ab2"`` and
+    ``"dpmpp_2m"`` are second-order multistep rules at one U-Net evaluation per step; additions, DESIGN.md "Multistep sampler"), and
+    ``schedule`` any module whose ``forward(num_steps + 1, device=)`` returns finite, strictly decreasing sigmas inside [0, 1].
+    ``forward(..., solver=, schedule=, sigmas=)`` override the constructor's choices for one call; ``sigmas`` are the ``num_steps + 1``
+    schedule values themselves."""
 
     diffusion_types = [VDiffusion]
 
-    def __init__(self, net: nn.Module, schedule: Optional[nn.Module] = None, use_graph: bool = True):
+    def __init__(self, net: nn.Module, schedule: Optional[nn.Module] = None, use_graph: bool = True, solver: str = "ddim"):
         super().__init__()
+        from .solvers import SOLVERS
+
+        if solver not in SOLVERS:
+            raise ValueError(f"unknown solver {solver!r}: expected one of {SOLVERS}")
         object.__setattr__(self, "_net", net)
         self.schedule = schedule if schedule is not None else LinearSchedule()
         self.use_graph = use_graph
+        self.solver = solver
 
     @property
     def net(self):
@@ -291,13 +324,30 @@ class VSampler(nn.Module):
 
     @torch.no_grad()
     def forward(self, x_noisy: Tensor, num_steps: int, show_progress: bool = False, *, embedding: Optional[Tensor] = None,
-                channels: Optional[Sequence[Tensor]] = None, embedding_scale: float = 1.0, **kwargs) -> Tensor:
+                channels: Optional[Sequence[Tensor]] = None, embedding_scale: float = 1.0, solver: Optional[str] = None,
+                sigmas=None, schedule: Optional[nn.Module] = None, **kwargs) -> Tensor:
         if kwargs:
             raise TypeError(f"unsupported sampling arguments: {sorted(kwargs)}")
-        if not isinstance(self.schedule, LinearSchedule) or (self.schedule.start, self.schedule.end) != (1.0, 0.0):
-            raise NotImplementedError("only LinearSchedule(1 -> 0) (the audio_diffusion_pytorch default) is implemented")
+        from .solvers import SOLVERS, check_sigmas, pack_table, solver_table
+
+        solver = self.solver if solver is None else solver
+        if solver not in SOLVERS:
+            raise ValueError(f"unknown solver {solver!r}: expected one of {SOLVERS}")
+        if sigmas is not None and schedule is not None:
+            raise ValueError("give `sigmas` or `schedule`, not both")
+        schedule = self.schedule if schedule is None else schedule
         assert embedding is not None, "ClassifierFreeGuidancePlugin requires embedding"
-        return self._net.engine().sample(x_noisy, num_steps, channels, embedding, embedding_scale, self.use_graph)
+        if sigmas is None and solver == "ddim" and _is_default_schedule(schedule):
+            return self._net.engine().sample(x_noisy, num_steps, channels, embedding, embedding_scale, self.use_graph)
+        if int(num_steps) < 1:
+            raise ValueError(f"num_steps must be >= 1, got {num_steps}")
+        if sigmas is None:
+            sigmas = schedule(int(num_steps) + 1, device=torch.device("cpu"))
+        if isinstance(sigmas, Tensor):
+            sigmas = sigmas.detach().to(device="cpu", dtype=torch.float32).numpy()
+        sig = check_sigmas(sigmas, num_steps)
+        return self._net.engine().sample_ms(x_noisy, sig, pack_table(solver_table(sig, solver)), channels, embedding, embedding_scale,
+                                            self.use_graph)
 
 
 def philox_normal(shape, seed: int, k: int, device, elem_offset: int = 0) -> Tensor:
@@ -322,7 +372,10 @@ class VInpainter(nn.Module):
     """``audio_diffusion_pytorch.VInpainter`` [RECALLED, UNPINNED: SURVEY.md A.6]: ``VSampler``'s loop with ``num_resamples`` evaluations
     per step; after each one the region where ``mask`` is True is replaced by the source re-noised to the iteration's level.  The whole
     loop runs inside ``sf_vinpaint``.  The noise is the device's counter-based generator (``philox_normal``), keyed by ``seed``; with
-    ``seed=None`` one seed is drawn from torch's CPU generator, so ``torch.manual_seed`` makes a run repeatable."""
+    ``seed=None`` one seed is drawn from torch's CPU generator, so ``torch.manual_seed`` makes a run repeatable.
+
+    The inpainter stays first order on ``LinearSchedule(1, 0)``: every iteration re-noises the kept region, so ``x`` is no longer on the
+    trajectory the previous ``x0_hat`` was taken from and the history a multistep rule (``VSampler(solver="ab2")``) needs is broken."""
 
     diffusion_types = [VDiffusion]
 

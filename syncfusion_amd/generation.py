@@ -14,6 +14,7 @@ clamped or quantised.
 """
 from __future__ import annotations
 
+import math
 import struct
 from pathlib import Path
 from typing import Iterable, List, Optional, Sequence, Union
@@ -32,8 +33,9 @@ Tensor = torch.Tensor
 def generate_batch(model, y: Tensor, z: Optional[Tensor] = None, text: Optional[Sequence[str]] = None, *,
                    num_steps: int = 150, length: int = 2 ** 18, embedding_scale: float = 7.5, cut_prefix: bool = False,
                    cond_text: bool = False, cut_length: Optional[int] = None, noise: Optional[Tensor] = None,
-                   generator: Optional[torch.Generator] = None) -> Tensor:
-    """One batch of main/generation.py:69-89,100 on the device of ``model``.  Returns ``(B, 1, cut_length)``."""
+                   generator: Optional[torch.Generator] = None, solver: Optional[str] = None, schedule=None) -> Tensor:
+    """One batch of main/generation.py:69-89,100 on the device of ``model``.  Returns ``(B, 1, cut_length)``.
+    ``solver`` / ``schedule`` (additions): ``VSampler``'s solver name and schedule module for this call; ``None`` keeps the sampler's own."""
     device = model.device
     _lib.require_gpu_tensor(torch.empty(0, device=device), "generate_batch")
     B = y.shape[0]
@@ -46,11 +48,47 @@ def generate_batch(model, y: Tensor, z: Optional[Tensor] = None, text: Optional[
     else:
         z_latent = model.clap_encode_audio(z.to(device))                          # :75
     gen = model.model.sample(x_noisy=noise.to(device), num_steps=num_steps, channels=y_latent["xs"][2:-1],
-                             embedding=z_latent.to(device), embedding_scale=embedding_scale)   # :77-83
+                             embedding=z_latent.to(device), embedding_scale=embedding_scale, **_solver_kwargs(solver, schedule))   # :77-83
     if cut_prefix:
         # one device pass for the batch (:86-89, :100); IndexError on a track without onsets, as the reference's [0] does
         return cut_prefix_crop(gen, y[:, :1], cut_length or length)
     return gen[:, :, : (cut_length or length)]                                     # :91,100
+
+
+def _solver_kwargs(solver, schedule) -> dict:
+    """Only what the caller chose reaches ``sample()``: with neither, the call is what it was."""
+    kw = {}
+    if solver is not None:
+        kw["solver"] = solver
+    if schedule is not None:
+        kw["schedule"] = schedule
+    return kw
+
+
+@torch.no_grad()
+def vary_batch(model, audio: Tensor, y: Tensor, z: Optional[Tensor] = None, text: Optional[Sequence[str]] = None, *, strength: float = 0.5,
+               num_steps: int = 50, embedding_scale: float = 7.5, cond_text: bool = False, seed: int = 0, solver: str = "ab2") -> Tensor:
+    """Variations of an existing clip ``audio`` ``(B, 1, L)`` under the onset track ``y`` and the CLAP conditioning: the clip is noised to
+    the level ``strength`` in (0, 1],
+
+        x_noisy = cos(strength * pi / 2) * audio + sin(strength * pi / 2) * philox_normal(audio.shape, seed, 0),
+
+    and sampled from there on ``LinearSchedule(strength, 0)`` with ``solver``.  Small ``strength`` stays close to the clip, 1 forgets
+    it.  The noise is the device's counter-based generator: a pure function of ``seed``."""
+    from .diffusion import LinearSchedule, philox_normal
+
+    if not 0.0 < float(strength) <= 1.0:
+        raise ValueError(f"strength must lie in (0, 1], got {strength}")
+    device = model.device
+    _lib.require_gpu_tensor(torch.empty(0, device=device), "vary_batch")
+    if audio.dim() != 3:
+        raise ValueError(f"audio must be (B, 1, L), got shape {tuple(audio.shape)}")
+    angle = float(strength) * math.pi / 2
+    x_noisy = math.cos(angle) * audio.to(device).to(torch.float32) + math.sin(angle) * philox_normal(tuple(audio.shape), seed, 0, device)
+    _, y_latent = model.onsets_encoder(y.to(device), with_info=True)
+    z_latent = _embed(model, z, text, cond_text, device)
+    return model.model.sample(x_noisy=x_noisy, num_steps=num_steps, channels=y_latent["xs"][2:-1], embedding=z_latent,
+                              embedding_scale=embedding_scale, solver=solver, schedule=LinearSchedule(float(strength), 0.0))
 
 
 def regions_to_keep_mask(regions, B: int, L: int) -> Tensor:
@@ -277,7 +315,8 @@ def generate_dataset(experiment_path: Union[str, Path], model, dataset: Iterable
                      model_path: Optional[str] = None, batch_size: int = 16, num_workers: int = 4, sample_rate: int = 48000,
                      num_steps: int = 150, length: int = 2 ** 18, embedding_scale: float = 7.5, cut_prefix: bool = False,
                      cond_text: bool = False, one_chunk_per_track: bool = False, cut_length: Optional[int] = None,
-                     downsample_rate: Optional[int] = None, save_cond: bool = False) -> List[Path]:
+                     downsample_rate: Optional[int] = None, save_cond: bool = False, solver: Optional[str] = None,
+                     schedule=None) -> List[Path]:
     """Same signature as main/generation.py:12-30.  ``dataset``: the reference's un-batched chunk dataset (batched here with
     ``batch_size`` / ``num_workers`` + ``collate_fn``, :37-38) or an iterable of already-collated batches (``iter_batches``)."""
     experiment_path = Path(experiment_path)
@@ -297,7 +336,7 @@ def generate_dataset(experiment_path: Union[str, Path], model, dataset: Iterable
                 chunk_id += B
                 continue
         gen = generate_batch(model, y, z, text, num_steps=num_steps, length=length, embedding_scale=embedding_scale,
-                             cut_prefix=cut_prefix, cond_text=cond_text, cut_length=cut_length)
+                             cut_prefix=cut_prefix, cond_text=cond_text, cut_length=cut_length, solver=solver, schedule=schedule)
         out_sr = sample_rate
         cond = z.to(gen.device).to(torch.float32) if (save_cond and not cond_text) else None   # :93-96: the conditioning audio itself
         if downsample_rate:                                                       # :90-98, on the device instead of the CPU
