@@ -149,6 +149,21 @@ int64_t sf_vsample_ms_workspace_bytes(const sf_unet *h, int B, int L0, int two_p
 int sf_vsample_ms(sf_unet *h, float *x_inout, const float *const *ctx, const float *emb, int B, int L0, int num_steps, float embedding_scale,
                   const float *sigmas, const float *table, int use_graph, void *ws, int64_t ws_bytes, void *stream);
 
+/* sf_vsample_ms with a guidance schedule ("Guidance schedules"; an addition, not part of the reference):
+ *   scales: HOST, num_steps rows of B finite floats, scales[i * B + b] = guidance scale of clip b at step i; NULL = 1 everywhere.
+ *   rescale: phi in [0, 1].  Step i uses  g = s == 1 ? v_c : v_u + (v_c - v_u) * s  and, where phi > 0,  v = g * (1 + phi * (std(v_c) / std(g) - 1))
+ *   with the standard deviations over all elements of the clip; v enters the solver row as in sf_vsample_ms.
+ *   No scale other than 1 in the call: the unconditional half is not evaluated (B rows per step, not 2 B) and the call is sf_vsample_ms's at
+ *   embedding_scale 1, step graph included.  Otherwise every step evaluates 2 B rows; its graph is cached apart, keyed on phi but not on the
+ *   scales: a later table of the same shape replays it.
+ *   hist_io: device, B * in_channels * L0 floats, or NULL.  Non-NULL: the history X_{i-1} the loop starts from and, on return, the one it ended
+ *   with, so that a schedule can be cut into consecutive calls -- each with its slice of sigmas, scales and of the table built for the WHOLE
+ *   schedule (row 0 of a continuing call has c1 != 0).  NULL: X_{-1} = 0, as in sf_vsample_ms.
+ *   Workspace: sf_vsample_gx_workspace_bytes (two_pass = any scale != 1). */
+int64_t sf_vsample_gx_workspace_bytes(const sf_unet *h, int B, int L0, int two_pass, int num_steps);
+int sf_vsample_gx(sf_unet *h, float *x_inout, const float *const *ctx, const float *emb, int B, int L0, int num_steps, const float *sigmas,
+                  const float *table, const float *scales, float rescale, float *hist_io, int use_graph, void *ws, int64_t ws_bytes, void *stream);
+
 /* Debug taps (tests only): after the next sf_unet_forward, every block-level activation is
  * copied as fp32 channels-last rows into `buf` (device).  Query the table afterwards. */
 int sf_unet_debug_enable(sf_unet *h, float *buf, int64_t cap_floats);
@@ -321,6 +336,20 @@ int sf_op_vinpaint_update(float *x, const float *v, const float *v_uncond, float
  * The result of an element does not depend on how [0, n) is cut into ranges, nor on the alignment of the pointers. */
 int sf_op_vsampler_update_ms(float *x, const float *v, const float *v_uncond, float scale, float *hist, const float *table,
                              const int32_t *step_idx, int64_t e0, int64_t e1, void *stream);
+/* Guidance schedules at op level ("Guidance schedules").  gtab: device, rows of B guidance scales, row k = *step_idx; clip_len: elements
+ * per clip; every tensor pointer is the base of the WHOLE (B, clip_len) tensor.
+ * sf_op_guidance_stats: for every clip, (count, mean, M2) of v and of the guided direction  g = s == 1 ? v : v_uncond + (v - v_uncond) * s
+ * (v_uncond may be NULL: g = v), reduced in fp64 without atomics into `part` (device, 8-byte aligned, sf_op_guidance_stats_bytes(B, clip_len)).
+ * sf_op_vsampler_update_g: sf_op_vsampler_update_ms with that g and, where rescale = phi > 0,  v = g * (1 + phi * (std(v) / std(g) - 1))  per
+ * clip, the factor combined from `part` in fp64 and rounded once to fp32 (exactly 1 where std(g) == 0).  rescale == 0: `part` is not read and may
+ * be NULL.  factor_out: device, B floats, or NULL.  e1 <= B * clip_len.  The result of an element does not depend on how [0, n) is cut into
+ * ranges, nor on the alignment of the pointers; a clip whose scale is exactly 1 gets the bits it gets with v_uncond == NULL. */
+int64_t sf_op_guidance_stats_bytes(int B, int64_t clip_len);
+int sf_op_guidance_stats(const float *v, const float *v_uncond, const float *gtab, const int32_t *step_idx, int B, int64_t clip_len, void *part,
+                         int64_t part_bytes, void *stream);
+int sf_op_vsampler_update_g(float *x, const float *v, const float *v_uncond, float *hist, const float *table, const float *gtab,
+                            const int32_t *step_idx, const void *part, float rescale, int B, int64_t clip_len, float *factor_out, int64_t e0,
+                            int64_t e1, void *stream);
 /* out = conv1d(silu(groupnorm(x))) + bias (+ residual).  x:(B,L,C) and out/residual:(B,Lout,N) channels-last in
  * `dtype`; w:(N,C,taps) fp32 in PyTorch layout (packed internally); groups==0 -> no norm/activation;
  * upsample = nearest-neighbour factor applied before the convolution.  Lout = (L*upsample + 2*pad - taps)/stride + 1. */

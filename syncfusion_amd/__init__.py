@@ -10,6 +10,7 @@ from . import audio_features, autograd, clap, clap_text, denoise, evaluation, fa
 from .config import instantiate, instantiate_class, instantiate_frames_transforms, instantiate_model_yaml
 from .diffusion import DiffusionModel, LinearSchedule, PowerSchedule, UNetV0, VDiffusion, VInpainter, VSampler
 from .solvers import solver_table
+from .guidance import evaluation_rows, plan_segments, scale_table
 from .audio_features import MelSpectrogram, mel_filterbank, onset_detect, onset_strength
 from .denoise import SpectralGateConfig, chunk_rows, istft, merge_rows, reduce_noise, stft
 from .encoder1d import Encoder1d
@@ -40,5 +41,5 @@ __all__ = ["DiffusionModel", "UNetV0", "VDiffusion", "VSampler", "LinearSchedule
            "jpeg", "JpegInfo", "decode_jpeg_batch", "parse_jpeg", "run_onset_test",
            "clap", "ClapAudioConfig", "ClapAudioEmbedder", "clap_text", "ClapEmbedder", "ClapTextConfig", "ClapTokenizer",
            "denoise", "SpectralGateConfig", "reduce_noise", "stft", "istft", "chunk_rows", "merge_rows",
-           "solver_table", "PowerSchedule", "vary_batch"]
+           "solver_table", "PowerSchedule", "vary_batch", "scale_table", "plan_segments", "evaluation_rows"]
 __version__ = "0.1.0"

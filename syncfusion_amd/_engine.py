@@ -238,6 +238,45 @@ class UNetEngine(_Base):
                                          _lib.stream_ptr(self.device)), "sf_vsample_ms")
         return x
 
+    def sample_gx(self, x_noisy: torch.Tensor, sigmas, table, scales, segments, channels: Sequence[torch.Tensor], embedding: torch.Tensor,
+                  guidance_rescale: float = 0.0, use_graph: bool = True) -> torch.Tensor:
+        """The multistep loop under a guidance schedule: one ``sf_vsample_gx`` per segment of ``segments``
+        (``syncfusion_amd.guidance.plan_segments``), each with its slice of the ``T + 1`` host ``sigmas``, of the ``(T, 8)`` host fp32
+        ``table`` (built for the whole schedule) and of the ``(T, B)`` host fp32 ``scales``, with one history tensor threaded through.
+        ``x_noisy`` is left untouched."""
+        import numpy as np
+
+        _lib.require_gpu_tensor(x_noisy, "DiffusionModel.sample")
+        self._check_inputs(x_noisy, channels, embedding)
+        B, _, L0 = x_noisy.shape
+        sig = np.ascontiguousarray(sigmas, dtype=np.float32)
+        tab = np.ascontiguousarray(table, dtype=np.float32)
+        sc = np.ascontiguousarray(scales, dtype=np.float32)
+        T = sig.size - 1
+        if sig.ndim != 1 or T < 1 or tab.shape != (T, 8) or sc.shape != (T, B):
+            raise ValueError(f"expected T + 1 sigmas, a (T, 8) table and (T, B) scales, got shapes {sig.shape}, {tab.shape} and {sc.shape}")
+        segments = [(int(i0), int(i1), bool(two)) for i0, i1, two in segments]
+        if not segments or segments[0][0] != 0 or segments[-1][1] != T or any(a[1] != b[0] for a, b in zip(segments, segments[1:])) or \
+                any(i1 <= i0 for i0, i1, _ in segments):
+            raise ValueError(f"segments {segments} do not cover the steps 0 .. {T} in order")
+        with torch.cuda.device(self.device):
+            x = _lib.f32c(x_noisy).clone()
+            hist = torch.zeros_like(x)
+            ctx = [_lib.f32c(c) for c in channels]
+            emb = _lib.f32c(embedding)
+            # one buffer for both kinds of segment (and sized for at least 256 steps, as sample()'s): the cached step graphs hold its addresses
+            sizes = [self.lib.sf_vsample_gx_workspace_bytes(self.handle, B, L0, two, max(T, 256)) for two in (0, 1)]
+            if min(sizes) < 0:
+                raise _lib.SyncFusionAmdError(f"unsupported shape B={B}, L0={L0}: {self.lib.sf_last_error().decode()}")
+            ws = self._workspace(max(sizes), self.device)
+            for i0, i1, two in segments:
+                s_sig, s_tab = np.ascontiguousarray(sig[i0:i1 + 1]), np.ascontiguousarray(tab[i0:i1])
+                s_sc = np.ascontiguousarray(sc[i0:i1]) if two else None
+                check(self.lib.sf_vsample_gx(self.handle, x.data_ptr(), _lib.ptr_array(ctx), emb.data_ptr(), B, L0, i1 - i0, s_sig.ctypes.data,
+                                             s_tab.ctypes.data, s_sc.ctypes.data if two else None, float(guidance_rescale), hist.data_ptr(),
+                                             int(bool(use_graph)), ws.data_ptr(), ws.numel(), _lib.stream_ptr(self.device)), "sf_vsample_gx")
+        return x
+
     def inpaint(self, source: torch.Tensor, mask: torch.Tensor, num_steps: int, num_resamples: int, channels: Sequence[torch.Tensor],
                 embedding: torch.Tensor, embedding_scale: float = 1.0, x_noisy: Optional[torch.Tensor] = None, seed: int = 0,
                 use_graph: bool = True) -> torch.Tensor:

@@ -118,6 +118,14 @@ SYMBOLS = {
     "sf_vsample_ms": (_I, [_P, _P, C.POINTER(_P), _P, _I, _I, _I, _F, _P, _P, _I, _P, _L, _P]),
     # (x, v, v_uncond, scale, hist, table, step_idx, e0, e1, stream)
     "sf_op_vsampler_update_ms": (_I, [_P, _P, _P, _F, _P, _P, _P, _L, _L, _P]),
+    "sf_vsample_gx_workspace_bytes": (_L, [_P, _I, _I, _I, _I]),
+    # (h, x_inout, ctx, emb, B, L0, num_steps, sigmas_host, table_host, scales_host, rescale, hist_io, use_graph, ws, ws_bytes, stream)
+    "sf_vsample_gx": (_I, [_P, _P, C.POINTER(_P), _P, _I, _I, _I, _P, _P, _P, _F, _P, _I, _P, _L, _P]),
+    "sf_op_guidance_stats_bytes": (_L, [_I, _L]),
+    # (v, v_uncond, gtab, step_idx, B, clip_len, part, part_bytes, stream)
+    "sf_op_guidance_stats": (_I, [_P, _P, _P, _P, _I, _L, _P, _L, _P]),
+    # (x, v, v_uncond, hist, table, gtab, step_idx, part, rescale, B, clip_len, factor_out, e0, e1, stream)
+    "sf_op_vsampler_update_g": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _L, _P, _L, _L, _P]),
     "sf_op_philox_normal": (_I, [C.c_uint64, C.c_uint32, _L, _L, _P, _P]),
     "sf_op_vinpaint_update": (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _L, _L, _P]),
     "sf_unet_debug_enable": (_I, [_P, _P, _L]),

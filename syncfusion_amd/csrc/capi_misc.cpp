@@ -150,6 +150,36 @@ int sf_op_vsampler_update_ms(float *x, const float *v, const float *v_uncond, fl
   SF_API_END
 }
 
+int64_t sf_op_guidance_stats_bytes(int B, int64_t clip_len) {
+  if (B < 1 || clip_len < 1) return -1;
+  return (int64_t)B * guidance_stats_blocks(clip_len) * 6 * (int64_t)sizeof(double);
+}
+
+int sf_op_guidance_stats(const float *v, const float *v_uncond, const float *gtab, const int32_t *step_idx, int B, int64_t clip_len, void *part,
+                         int64_t part_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!v || !gtab || !step_idx || !part || B < 1 || clip_len < 1) fail(SF_ERR_INVALID, "bad argument");
+  if ((reinterpret_cast<uintptr_t>(part) & 7) != 0) fail(SF_ERR_INVALID, "partials buffer is not 8-byte aligned");
+  if (part_bytes < sf_op_guidance_stats_bytes(B, clip_len)) fail(SF_ERR_WORKSPACE, "partials buffer too small");
+  SF_HIP(launch_guidance_stats(v, v_uncond, gtab, step_idx, 0, B, clip_len, static_cast<double *>(part), static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
+int sf_op_vsampler_update_g(float *x, const float *v, const float *v_uncond, float *hist, const float *table, const float *gtab,
+                            const int32_t *step_idx, const void *part, float rescale, int B, int64_t clip_len, float *factor_out, int64_t e0,
+                            int64_t e1, void *stream) {
+  SF_API_BEGIN
+  if (!x || !v || !hist || !table || !gtab || !step_idx || B < 1 || clip_len < 1 || e0 < 0 || e1 < e0) fail(SF_ERR_INVALID, "bad argument");
+  if (e1 > (int64_t)B * clip_len) fail(SF_ERR_INVALID, "the range ends past the last clip");
+  if (!(rescale >= 0.0f && rescale <= 1.0f)) fail(SF_ERR_INVALID, "rescale must be inside [0, 1]");
+  if (rescale > 0.0f && (!part || (reinterpret_cast<uintptr_t>(part) & 7) != 0)) fail(SF_ERR_INVALID, "rescale > 0 needs the partials of sf_op_guidance_stats");
+  SF_HIP(launch_vsampler_update_g(x, v, v_uncond, hist, table, gtab, step_idx, 0, static_cast<const double *>(part), rescale, B, clip_len, factor_out,
+                                  e0, e1, static_cast<hipStream_t>(stream)));
+  return SF_OK;
+  SF_API_END
+}
+
 int sf_cut_prefix_crop(const float *gen, const float *y, int B, int C, int L, int cut_length, float *out, int32_t *first_onset, void *stream) {
   SF_API_BEGIN
   if (!gen || !y || !out || !first_onset || B < 1 || C < 1 || L < 1 || cut_length < 1 || cut_length > L) fail(SF_ERR_INVALID, "bad argument");

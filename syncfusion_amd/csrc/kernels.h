@@ -382,6 +382,17 @@ hipError_t launch_vinpaint_update(float *x, const float *v, const float *v_uncon
 //   (al, be, cx, c0, c1) = table[8k .. 8k+4],  k = *step_idx + step_bias  (rows of 8 floats, three unused).
 hipError_t launch_vsampler_update_ms(float *x, const float *v, const float *v_uncond, float scale, float *hist, const float *table,
                                      const int *step_idx, int step_bias, int64_t e0, int64_t e1, hipStream_t s);
+// Guidance schedules (sampler.hip; DESIGN.md, "Guidance schedules").  gtab: [steps][B] guidance scales, k = *step_idx + step_bias as above;
+// clip_len = C * L elements per clip.  launch_guidance_stats leaves guidance_stats_blocks(clip_len) fp64 partials (count, mean, M2 of v_c and of
+// the guided direction g; 6 doubles each) per clip in `part` (B * blocks * 6 doubles); v_uncond may be null (g = v_c).
+// launch_vsampler_update_g is launch_vsampler_update_ms with  g = s == 1 ? v_c : v_u + (v_c - v_u) * s,  s = gtab[k][clip], and, where phi > 0,
+// v = g * (1 + phi * (std(v_c) / std(g) - 1)) per clip from `part` (not read where phi == 0); fac_out: B floats or null.  e1 <= B * clip_len.
+int guidance_stats_blocks(int64_t clip_len);
+hipError_t launch_guidance_stats(const float *v, const float *v_uncond, const float *gtab, const int *step_idx, int step_bias, int B,
+                                 int64_t clip_len, double *part, hipStream_t s);
+hipError_t launch_vsampler_update_g(float *x, const float *v, const float *v_uncond, float *hist, const float *table, const float *gtab,
+                                    const int *step_idx, int step_bias, const double *part, float phi, int B, int64_t clip_len, float *fac_out,
+                                    int64_t e0, int64_t e1, hipStream_t s);
 // out[i] = standard normal of element (elem_offset + i) at virtual iteration k: Philox4x32-10 with counter (g lo, g hi, k, 0), g = element >> 2,
 // key (seed lo, seed hi), Box-Muller on u(w) = ((w >> 9) + 0.5) * 2^-23; lane = element & 3 ("Inpainting sampler")
 hipError_t launch_philox_normal(uint64_t seed, uint32_t k, int64_t elem_offset, int64_t n, float *out, hipStream_t s);

@@ -1,6 +1,6 @@
 // Inpainting sampler kernels: counter-based device noise (Philox4x32-10 + Box-Muller) and the fused VInpainter update
-// (v-sampler step + re-noised source blend); the linear multistep update of sf_vsample_ms.  HBM-bound streaming, one Philox group (four
-// consecutive elements) per thread.
+// (v-sampler step + re-noised source blend); the linear multistep update of sf_vsample_ms; the per-clip statistics and the guided update of
+// sf_vsample_gx (guidance schedules).  HBM-bound streaming, one Philox group (four consecutive elements) per thread.
 #include "common.h"
 #include "kernels.h"
 
@@ -230,7 +230,248 @@ __global__ void vsampler_update_ms_kernel(float *__restrict__ x, const float *__
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Guidance schedules ("Guidance schedules"): the scale of clip b at step k is gtab[k * B + b]; an optional per-clip rescale of the
+// guided direction to the level of v_c (Lin et al. 2023, section 3.4).
+// ---------------------------------------------------------------------------------------------------
+// the guided direction of one element: v_c itself where the scale is exactly 1 (or there is no unconditional half), else guide()
+__device__ __forceinline__ float guide_s(float vc, const float *__restrict__ vu, int64_t i, float sc) {
+  if (!vu || sc == 1.0f) return vc;
+  return guide(vc, vu[i], sc);
+}
+__device__ __forceinline__ float rescaled(float g, float fac) {
+#pragma clang fp contract(off)
+  return g * fac;
+}
+
+constexpr int kStatsPart = 6;   // doubles per partial: count, mean(v_c), M2(v_c), mean(g), M2(g), unused
+
+// sum of the TPB per-thread values in a fixed order (LDS tree); every thread gets the result
+__device__ __forceinline__ double block_sum(double val, double *sh) {
+  __syncthreads();
+  sh[threadIdx.x] = val;
+  __syncthreads();
+  for (int w = TPB / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// Statistics of v_c and of the guided direction g over one clip, for the rescale: grid (blocks per clip, B).  A block takes a contiguous share of
+// its clip and leaves (count, mean, M2) of both in fp64 -- two passes over its share (the mean first, then the squared deviations from it, with
+// the first-order correction), the second one from cache -- in part[(b * gridDim.x + block) * kStatsPart ..].  No atomics, a fixed order of
+// additions: a replay gives the same bits, and so does a launch from pointers with another alignment (a thread adds the same elements in
+// the same order on the 16-byte path and element by element).  v, vu: bases of the WHOLE (B, C, L) tensors; vu may be null (g = v_c).
+__global__ void guidance_stats_kernel(const float *__restrict__ v, const float *__restrict__ vu, const float *__restrict__ gtab,
+                                      const int *__restrict__ step_idx, int step_bias, int B, int64_t clip_len, double *__restrict__ part, int vec) {
+  __shared__ double sh[TPB];
+  const int b = blockIdx.y, nb = gridDim.x;
+  const int k = *step_idx + step_bias;
+  const float sc = gtab[(int64_t)k * B + b];
+  const int64_t per = (clip_len + nb - 1) / nb;
+  const int64_t base = (int64_t)b * clip_len;
+  int64_t lo = base + (int64_t)blockIdx.x * per, hi = lo + per;
+  if (hi > base + clip_len) hi = base + clip_len;
+  if (lo > hi) lo = hi;
+  const int64_t g_lo = lo >> 2, ng = hi > lo ? ((hi + 3) >> 2) - g_lo : 0;
+  double mc = 0.0, mg = 0.0, m2c = 0.0, m2g = 0.0;
+  for (int pass = 0; pass < 2; ++pass) {
+    double a_c = 0.0, a_g = 0.0, q_c = 0.0, q_g = 0.0;
+    auto add = [&](float c, float g) {   // one element, in the element order of the thread's groups on either path
+      if (pass == 0) {
+        a_c += (double)c;
+        a_g += (double)g;
+      } else {
+        const double dc = (double)c - mc, dg = (double)g - mg;
+        a_c += dc;
+        a_g += dg;
+        q_c += dc * dc;
+        q_g += dg * dg;
+      }
+    };
+    for (int64_t t = threadIdx.x; t < ng; t += TPB) {
+      const int64_t e = 4 * (g_lo + t);
+      if (vec && e >= lo && e + 4 <= hi) {
+        const float4 vv = *reinterpret_cast<const float4 *>(v + e);
+        if (vu && sc != 1.0f) {
+          const float4 m = *reinterpret_cast<const float4 *>(vu + e);
+          add(vv.x, guide(vv.x, m.x, sc));
+          add(vv.y, guide(vv.y, m.y, sc));
+          add(vv.z, guide(vv.z, m.z, sc));
+          add(vv.w, guide(vv.w, m.w, sc));
+        } else {
+          add(vv.x, vv.x);
+          add(vv.y, vv.y);
+          add(vv.z, vv.z);
+          add(vv.w, vv.w);
+        }
+      } else {
+        for (int l = 0; l < 4; ++l) {
+          const int64_t i = e + l;
+          if (i < lo || i >= hi) continue;
+          const float c = v[i];
+          add(c, guide_s(c, vu, i, sc));
+        }
+      }
+    }
+    const double cntd = (double)(hi - lo);
+    if (pass == 0) {
+      const double s_c = block_sum(a_c, sh), s_g = block_sum(a_g, sh);
+      if (hi > lo) mc = s_c / cntd, mg = s_g / cntd;
+    } else {
+      const double s_c = block_sum(a_c, sh), s_g = block_sum(a_g, sh), t_c = block_sum(q_c, sh), t_g = block_sum(q_g, sh);
+      if (hi > lo) {
+        m2c = t_c - s_c * s_c / cntd;   // (the sum of the deviations from the rounded mean is ~0: the textbook correction)
+        m2g = t_g - s_g * s_g / cntd;
+        if (m2c < 0.0) m2c = 0.0;
+        if (m2g < 0.0) m2g = 0.0;
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    double *o = part + ((int64_t)b * nb + blockIdx.x) * kStatsPart;
+    o[0] = (double)(hi - lo);
+    o[1] = mc;
+    o[2] = m2c;
+    o[3] = mg;
+    o[4] = m2g;
+    o[5] = 0.0;
+  }
+}
+
+// The rescale factor of clip b from its npart partials: Chan's pairwise update in fp64, partial after partial in index order, then
+//   r = sqrt(M2(v_c) / M2(g)),  factor = 1 + phi (r - 1), rounded once to fp32;  exactly 1 where M2(g) == 0.
+__device__ float rescale_factor(const double *__restrict__ part, int npart, int b, float phi) {
+  const double *p = part + (int64_t)b * npart * kStatsPart;
+  double n = 0.0, mc = 0.0, m2c = 0.0, mg = 0.0, m2g = 0.0;
+  for (int j = 0; j < npart; ++j, p += kStatsPart) {
+    const double nj = p[0];
+    if (!(nj > 0.0)) continue;
+    const double nn = n + nj, w = nj / nn, dc = p[1] - mc, dg = p[3] - mg;
+    mc += dc * w;
+    mg += dg * w;
+    m2c += p[2] + dc * dc * (n * w);
+    m2g += p[4] + dg * dg * (n * w);
+    n = nn;
+  }
+  if (!(m2g > 0.0)) return 1.0f;
+  return (float)(1.0 + (double)phi * (sqrt(m2c / m2g) - 1.0));
+}
+
+constexpr int kFacCache = 32;   // clips whose factor a workgroup keeps in LDS (its contiguous share of the range rarely touches more than two)
+
+// The multistep update with a guidance schedule (range convention of vsampler_update_ms_kernel: whole-tensor bases, elements [e0, e1)):
+//   g = s == 1 ? v_c : guide(v_c, v_u, s),   v = phi > 0 ? g * factor(clip) : g,   then the solver row exactly as vsampler_update_ms_kernel,
+//   s = gtab[k * B + clip],  clip = element / clip_len,  row = table + 8 k,  k = *step_idx + step_bias.
+// Each workgroup takes a CONTIGUOUS share of the range's 4-groups, so it needs the factors of few clips: it combines their partials once, into
+// LDS (rescale_factor; element by element where a share touches more than kFacCache clips -- the same function, the same bits).  A 4-group takes
+// the 16-byte path only where it lies inside the range and inside one clip.  Nothing that changes between calls is an argument except phi and B.
+__global__ void vsampler_update_g_kernel(float *__restrict__ x, const float *__restrict__ v, const float *__restrict__ vu, float *__restrict__ hist,
+                                         const float *__restrict__ table, const float *__restrict__ gtab, const int *__restrict__ step_idx,
+                                         int step_bias, const double *__restrict__ part, int npart, float phi, int B, int64_t clip_len,
+                                         float *__restrict__ fac_out, int64_t e0, int64_t e1, int vec) {
+  __shared__ float fac_sh[kFacCache];
+  const int k = *step_idx + step_bias;
+  const float *row = table + 8 * (int64_t)k;
+  const float al = row[0], be = row[1], cx = row[2], c0 = row[3], c1 = row[4];
+  const float *srow = gtab + (int64_t)k * B;
+  const bool resc = phi > 0.0f;
+  const int64_t g_lo = e0 >> 2, ng = ((e1 + 3) >> 2) - g_lo;
+  const int64_t per = (ng + gridDim.x - 1) / gridDim.x;
+  int64_t t_lo = (int64_t)blockIdx.x * per, t_hi = t_lo + per;
+  if (t_hi > ng) t_hi = ng;
+  if (fac_out && blockIdx.x == 0)
+    for (int b = threadIdx.x; b < B; b += blockDim.x) fac_out[b] = resc ? rescale_factor(part, npart, b, phi) : 1.0f;
+  if (t_lo >= t_hi) return;
+  // clips of the first and the last element of this workgroup's share
+  int64_t f_lo = 4 * (g_lo + t_lo), f_hi = 4 * (g_lo + t_hi);
+  if (f_lo < e0) f_lo = e0;
+  if (f_hi > e1) f_hi = e1;
+  const int64_t c_first = f_lo / clip_len, c_last = (f_hi - 1) / clip_len;
+  const bool cached = resc && c_last - c_first < kFacCache;
+  if (cached) {
+    for (int64_t c = c_first + threadIdx.x; c <= c_last; c += blockDim.x) fac_sh[c - c_first] = rescale_factor(part, npart, (int)c, phi);
+    __syncthreads();
+  }
+  const bool narrow = e1 <= (int64_t)0x7fffffff && clip_len <= (int64_t)0x7fffffff;   // 32-bit division for the clip index where both fit
+  for (int64_t t = t_lo + threadIdx.x; t < t_hi; t += blockDim.x) {
+    const int64_t e = 4 * (g_lo + t);
+    const int64_t c = narrow ? (int64_t)((uint32_t)e / (uint32_t)clip_len) : e / clip_len;
+    const bool one_clip = e - c * clip_len + 4 <= clip_len;
+    if (vec && one_clip && e >= e0 && e + 4 <= e1) {
+      const float sc = srow[c];
+      const float4 xx = *reinterpret_cast<const float4 *>(x + e);
+      const float4 hh = *reinterpret_cast<const float4 *>(hist + e);
+      float4 vv = *reinterpret_cast<const float4 *>(v + e);
+      if (vu && sc != 1.0f) {
+        const float4 m = *reinterpret_cast<const float4 *>(vu + e);
+        vv.x = guide(vv.x, m.x, sc);
+        vv.y = guide(vv.y, m.y, sc);
+        vv.z = guide(vv.z, m.z, sc);
+        vv.w = guide(vv.w, m.w, sc);
+      }
+      if (resc) {
+        const float fac = cached ? fac_sh[c - c_first] : rescale_factor(part, npart, (int)c, phi);
+        vv.x = rescaled(vv.x, fac);
+        vv.y = rescaled(vv.y, fac);
+        vv.z = rescaled(vv.z, fac);
+        vv.w = rescaled(vv.w, fac);
+      }
+      float4 X, o;
+      X.x = ms_x0(xx.x, vv.x, al, be);
+      X.y = ms_x0(xx.y, vv.y, al, be);
+      X.z = ms_x0(xx.z, vv.z, al, be);
+      X.w = ms_x0(xx.w, vv.w, al, be);
+      o.x = ms_next(xx.x, X.x, hh.x, cx, c0, c1);
+      o.y = ms_next(xx.y, X.y, hh.y, cx, c0, c1);
+      o.z = ms_next(xx.z, X.z, hh.z, cx, c0, c1);
+      o.w = ms_next(xx.w, X.w, hh.w, cx, c0, c1);
+      *reinterpret_cast<float4 *>(x + e) = o;
+      *reinterpret_cast<float4 *>(hist + e) = X;
+    } else {
+      for (int l = 0; l < 4; ++l) {
+        const int64_t i = e + l;
+        if (i < e0 || i >= e1) continue;
+        const int64_t ci = (i - c * clip_len >= clip_len) ? i / clip_len : c;   // (a clip shorter than a group: past the next one too)
+        float vv = guide_s(v[i], vu, i, srow[ci]);
+        if (resc) vv = rescaled(vv, cached ? fac_sh[ci - c_first] : rescale_factor(part, npart, (int)ci, phi));
+        const float xx = x[i];
+        const float X = ms_x0(xx, vv, al, be);
+        x[i] = ms_next(xx, X, hist[i], cx, c0, c1);
+        hist[i] = X;
+      }
+    }
+  }
+}
+
 }  // namespace
+
+int guidance_stats_blocks(int64_t clip_len) {
+  int64_t nb = (clip_len + 4095) / 4096;   // 16 elements per thread and pass
+  return (int)(nb < 1 ? 1 : (nb > 64 ? 64 : nb));
+}
+
+hipError_t launch_guidance_stats(const float *v, const float *v_uncond, const float *gtab, const int *step_idx, int step_bias, int B,
+                                 int64_t clip_len, double *part, hipStream_t s) {
+  if (B < 1 || clip_len < 1) return hipSuccess;
+  auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const int vec = al16(v) && (!v_uncond || al16(v_uncond));
+  hipLaunchKernelGGL(guidance_stats_kernel, dim3((unsigned)guidance_stats_blocks(clip_len), (unsigned)B), dim3(TPB), 0, s, v, v_uncond, gtab, step_idx,
+                     step_bias, B, clip_len, part, vec);
+  return hipGetLastError();
+}
+
+hipError_t launch_vsampler_update_g(float *x, const float *v, const float *v_uncond, float *hist, const float *table, const float *gtab,
+                                    const int *step_idx, int step_bias, const double *part, float phi, int B, int64_t clip_len, float *fac_out,
+                                    int64_t e0, int64_t e1, hipStream_t s) {
+  if (e1 <= e0) return hipSuccess;
+  auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const int vec = al16(x) && al16(v) && (!v_uncond || al16(v_uncond)) && al16(hist);
+  hipLaunchKernelGGL(vsampler_update_g_kernel, grid_for((e1 - e0 + 3) / 4 + 1), dim3(TPB), 0, s, x, v, v_uncond, hist, table, gtab, step_idx, step_bias,
+                     part, guidance_stats_blocks(clip_len), phi, B, clip_len, fac_out, e0, e1, vec);
+  return hipGetLastError();
+}
 
 hipError_t launch_vsampler_update_ms(float *x, const float *v, const float *v_uncond, float scale, float *hist, const float *table,
                                      const int *step_idx, int step_bias, int64_t e0, int64_t e1, hipStream_t s) {

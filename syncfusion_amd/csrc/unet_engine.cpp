@@ -88,6 +88,9 @@ struct Plan {  // everything carved out of the caller's workspace for one (B, L0
   // multistep loop only (sf_vsample_ms): X_{i-1} of every element and the coefficient table [steps][8] the update kernel reads
   float *hist = nullptr;
   float *table = nullptr;
+  // guidance schedule only (sf_vsample_gx with a scale other than 1): the scales [steps][B] and the fp64 partial statistics of the rescale
+  float *gtab = nullptr;
+  double *gpart = nullptr;
 };
 
 }  // namespace
@@ -146,10 +149,12 @@ struct sf_unet {
     bool two = false, valid = false;
     bool inpaint = false;   // sf_vinpaint's step (other update kernel, other workspace layout) never replays sf_vsample's, nor the reverse
     bool multistep = false; // nor does sf_vsample_ms's step replay as either of them, nor they as it
+    bool guided = false;    // sf_vsample_gx with a scale table: the scales are read from the workspace (`scale` is 0), the rescale weight is baked in
+    float phi = 0.f;
     float scale = 0.f;
     const void *ws = nullptr;
     bool operator==(const GraphKey &o) const {
-      return valid && o.valid && inpaint == o.inpaint && multistep == o.multistep && B == o.B && L0 == o.L0 && T == o.T && nbr == o.nbr && two == o.two && scale == o.scale && ws == o.ws;
+      return valid && o.valid && inpaint == o.inpaint && multistep == o.multistep && guided == o.guided && phi == o.phi && B == o.B && L0 == o.L0 && T == o.T && nbr == o.nbr && two == o.two && scale == o.scale && ws == o.ws;
     }
   } gkey;
   // Step graphs of OTHER recently used (shape, workspace, guidance) combinations: a server alternating between a few request
@@ -615,7 +620,7 @@ void build(sf_unet &u, const WeightMap *wm, hipStream_t s) {
 constexpr int kSchedSteps = 1024;   // schedule capacity that keeps the workspace layout independent of num_steps
 constexpr int64_t kMaxVirtualSteps = 1 << 24;   // sf_vinpaint: num_steps * num_resamples (an int row count everywhere below)
 
-Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num_steps, bool inpaint = false, bool multistep = false) {
+Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num_steps, bool inpaint = false, bool multistep = false, bool guided = false) {
   const sf_unet_config &c = u.cfg;
   Plan p;
   p.B = B;
@@ -766,6 +771,12 @@ Plan make_plan(const sf_unet &u, Workspace &ws, int B, int L0, bool two, int num
   if (multistep) {
     p.hist = ws.alloc_n<float>((int64_t)B * L0 * c.in_channels);
     p.table = ws.alloc_n<float>(8 * ns);
+  }
+  // The guidance schedule's, only in ITS layout (behind the multistep loop's, whose addresses stay what they are): the scale table (fixed capacity,
+  // like the coefficient table) and the per-clip partial statistics the rescale reads.
+  if (guided) {
+    p.gtab = ws.alloc_n<float>(ns * B);
+    p.gpart = ws.alloc_n<double>((int64_t)B * guidance_stats_blocks((int64_t)L0 * c.in_channels) * 6);
   }
   // Everything whose SIZE depends on the number of steps comes last, so that no other address does: a step graph
   // instantiated for one num_steps stays valid for another (up to kSchedSteps; the tables are indexed by the device
@@ -1713,10 +1724,11 @@ struct Exec {
   }
 };
 
-void check_ws(const sf_unet *h, void *ws, int64_t ws_bytes, int B, int L0, bool two, int steps, bool inpaint = false, bool multistep = false) {
+void check_ws(const sf_unet *h, void *ws, int64_t ws_bytes, int B, int L0, bool two, int steps, bool inpaint = false, bool multistep = false,
+              bool guided = false) {
   if (!ws) fail(SF_ERR_WORKSPACE, "workspace is null");
   Workspace dry(nullptr, 0);
-  make_plan(*h, dry, B, L0, two, steps, inpaint, multistep);
+  make_plan(*h, dry, B, L0, two, steps, inpaint, multistep, guided);
   if (dry.used() > ws_bytes) fail(SF_ERR_WORKSPACE, "workspace too small: need %lld bytes, have %lld", (long long)dry.used(), (long long)ws_bytes);
 }
 
@@ -1845,16 +1857,26 @@ struct MultistepArgs {
   const float *sigmas;   // host, num_steps + 1
   const float *table;    // host, num_steps rows of 8
 };
+// `ga` != nullptr (only with `ms`): sf_vsample_gx.  With a scale table the step evaluates both halves, reduces the rescale statistics (phi > 0) and
+// applies the guided update launch, all on the loop's stream; without one (no scale other than 1 in the call) the loop is sf_vsample_ms's at scale 1.
+// Either way the history starts from and ends in hist_io when that is given.
+struct GuidanceArgs {
+  const float *scales;   // host, num_steps rows of B, or nullptr: single-pass call
+  float rescale;         // phi
+  float *hist_io;        // device, n floats, or nullptr
+};
 
 static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const float *const *ctx, const float *emb, int B, int L0, int num_steps,
-                        float embedding_scale, int use_graph, void *ws, int64_t ws_bytes, void *stream, const MultistepArgs *ms = nullptr) {
-  const char *const tag = inp ? "sf_vinpaint" : (ms ? "sf_vsample_ms" : "sf_vsample");
+                        float embedding_scale, int use_graph, void *ws, int64_t ws_bytes, void *stream, const MultistepArgs *ms = nullptr,
+                        const GuidanceArgs *ga = nullptr) {
+  const char *const tag = inp ? "sf_vinpaint" : (ga ? "sf_vsample_gx" : (ms ? "sf_vsample_ms" : "sf_vsample"));
   const int R = inp ? inp->num_resamples : 1;
   const int T = num_steps * R;   // (virtual) steps of the loop
-  const bool two = embedding_scale != 1.0f;
-  check_ws(h, ws, ws_bytes, B, L0, two, T, inp != nullptr, ms != nullptr);
+  const bool guided = ga && ga->scales;
+  const bool two = guided || embedding_scale != 1.0f;
+  check_ws(h, ws, ws_bytes, B, L0, two, T, inp != nullptr, ms != nullptr, guided);
   Workspace w(ws, ws_bytes);
-  Plan p = make_plan(*h, w, B, L0, two, T, inp != nullptr, ms != nullptr);
+  Plan p = make_plan(*h, w, B, L0, two, T, inp != nullptr, ms != nullptr, guided);
   hipStream_t user = static_cast<hipStream_t>(stream);
   hipStream_t s = user;
   if (use_graph && T > 1) {
@@ -1940,8 +1962,10 @@ static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const floa
   // c1 == 0, but 0 * (whatever the workspace held) may be NaN.
   if (ms) {
     SF_HIP(hipMemcpyAsync(p.table, ms->table, 8 * (size_t)T * sizeof(float), hipMemcpyHostToDevice, s));
-    SF_HIP(hipMemsetAsync(p.hist, 0, n * sizeof(float), s));
+    if (ga && ga->hist_io) SF_HIP(hipMemcpyAsync(p.hist, ga->hist_io, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else SF_HIP(hipMemsetAsync(p.hist, 0, n * sizeof(float), s));
   }
+  if (guided) SF_HIP(hipMemcpyAsync(p.gtab, ga->scales, (size_t)T * B * sizeof(float), hipMemcpyHostToDevice, s));
   // sigma_i is the same for every clip, so the time MLP and the 42 Modulation / SkipModulate projections of ALL steps
   // are one set of GEMMs with M = num_steps, once per call (instead of five launches inside every step); a step then
   // starts by selecting its row (which also advances the device step counter) and every consumer reads that one row
@@ -1956,7 +1980,13 @@ static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const floa
   // the update launch of the elements [e0, e1) on stream `su`; `ahead`: the step counter has already been advanced (*counter == i + 1)
   auto update = [&](int64_t e0, int64_t e1, const int *counter, bool ahead, hipStream_t su) {
     const float *vu = two ? p.vout + n : nullptr;
-    if (inp)
+    if (guided) {
+      // (always the whole tensor on the loop's stream: guidance keeps the clips of a step together)
+      const int64_t clip_len = n / B;
+      if (ga->rescale > 0.0f) SF_HIP(launch_guidance_stats(p.vout, vu, p.gtab, counter, ahead ? -1 : 0, B, clip_len, p.gpart, su));
+      SF_HIP(launch_vsampler_update_g(xs, p.vout, vu, p.hist, p.table, p.gtab, counter, ahead ? -1 : 0, p.gpart, ga->rescale, B, clip_len, nullptr, e0,
+                                      e1, su));
+    } else if (inp)
       SF_HIP(launch_vinpaint_update(xs, p.vout, vu, embedding_scale, p.src, p.mask, sched, counter, ahead ? -1 : 0, p.seed, e0, e1, su));
     else if (ms)
       SF_HIP(launch_vsampler_update_ms(xs, p.vout, vu, embedding_scale, p.hist, p.table, counter, ahead ? -1 : 0, e0, e1, su));
@@ -1983,7 +2013,9 @@ static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const floa
   key.two = two;
   key.inpaint = inp != nullptr;
   key.multistep = ms != nullptr;
-  key.scale = embedding_scale;
+  key.guided = guided;
+  key.phi = guided ? ga->rescale : 0.f;
+  key.scale = guided ? 0.f : embedding_scale;
   key.ws = ws;
   key.valid = true;
   if (use_graph && T > 1 && !h->prof_on) h->activate_graphs(key);
@@ -2108,6 +2140,7 @@ static void run_sampler(sf_unet *h, float *x, const InpaintArgs *inp, const floa
   }
   }
   SF_HIP(hipMemcpyAsync(x, xs, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (ga && ga->hist_io) SF_HIP(hipMemcpyAsync(ga->hist_io, p.hist, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (s != user) {
     SF_HIP(hipEventRecord(h->ev_out, s));
     SF_HIP(hipStreamWaitEvent(user, h->ev_out, 0));
@@ -2124,6 +2157,15 @@ int sf_vsample(sf_unet *h, float *x, const float *const *ctx, const float *emb, 
   run_sampler(h, x, nullptr, ctx, emb, B, L0, num_steps, embedding_scale, use_graph, ws, ws_bytes, stream);
   return SF_OK;
   SF_API_END
+}
+
+static void check_ms_tables(const float *sigmas, const float *table, int num_steps) {
+  for (int i = 0; i <= num_steps; ++i) {
+    if (!(sigmas[i] >= 0.0f && sigmas[i] <= 1.0f)) fail(SF_ERR_INVALID, "sigmas[%d] = %g is not inside [0, 1]", i, (double)sigmas[i]);
+    if (i > 0 && !(sigmas[i] < sigmas[i - 1])) fail(SF_ERR_INVALID, "sigmas must be strictly decreasing (at %d)", i);
+  }
+  for (int64_t i = 0; i < 8 * (int64_t)num_steps; ++i)
+    if (!std::isfinite(table[i])) fail(SF_ERR_INVALID, "solver table entry %lld is not finite", (long long)i);
 }
 
 int64_t sf_vsample_ms_workspace_bytes(const sf_unet *h, int B, int L0, int two_pass, int num_steps) {
@@ -2144,14 +2186,43 @@ int sf_vsample_ms(sf_unet *h, float *x, const float *const *ctx, const float *em
   if (!h || !x || !ctx || !sigmas || !table) fail(SF_ERR_INVALID, "null argument");
   if (!emb) fail(SF_ERR_INVALID, "ClassifierFreeGuidancePlugin requires embedding");
   if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
-  for (int i = 0; i <= num_steps; ++i) {
-    if (!(sigmas[i] >= 0.0f && sigmas[i] <= 1.0f)) fail(SF_ERR_INVALID, "sigmas[%d] = %g is not inside [0, 1]", i, (double)sigmas[i]);
-    if (i > 0 && !(sigmas[i] < sigmas[i - 1])) fail(SF_ERR_INVALID, "sigmas must be strictly decreasing (at %d)", i);
-  }
-  for (int64_t i = 0; i < 8 * (int64_t)num_steps; ++i)
-    if (!std::isfinite(table[i])) fail(SF_ERR_INVALID, "solver table entry %lld is not finite", (long long)i);
+  check_ms_tables(sigmas, table, num_steps);
   const MultistepArgs ms{sigmas, table};
   run_sampler(h, x, nullptr, ctx, emb, B, L0, num_steps, embedding_scale, use_graph, ws, ws_bytes, stream, &ms);
+  return SF_OK;
+  SF_API_END
+}
+
+int64_t sf_vsample_gx_workspace_bytes(const sf_unet *h, int B, int L0, int two_pass, int num_steps) {
+  try {
+    if (!h) fail(SF_ERR_INVALID, "null handle");
+    if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
+    Workspace dry(nullptr, 0);
+    make_plan(*h, dry, B, L0, two_pass != 0, num_steps, false, true, two_pass != 0);
+    return dry.used();
+  } catch (const EngineError &) {
+    return -1;
+  }
+}
+
+int sf_vsample_gx(sf_unet *h, float *x, const float *const *ctx, const float *emb, int B, int L0, int num_steps, const float *sigmas,
+                  const float *table, const float *scales, float rescale, float *hist_io, int use_graph, void *ws, int64_t ws_bytes, void *stream) {
+  SF_API_BEGIN
+  if (!h || !x || !ctx || !sigmas || !table) fail(SF_ERR_INVALID, "null argument");
+  if (!emb) fail(SF_ERR_INVALID, "ClassifierFreeGuidancePlugin requires embedding");
+  if (num_steps < 1) fail(SF_ERR_INVALID, "num_steps must be >= 1");
+  if (B < 1) fail(SF_ERR_INVALID, "B must be >= 1");
+  check_ms_tables(sigmas, table, num_steps);
+  if (!(rescale >= 0.0f && rescale <= 1.0f)) fail(SF_ERR_INVALID, "rescale = %g is not inside [0, 1]", (double)rescale);
+  bool any = false;   // `two` of this call: any scale other than 1
+  if (scales)
+    for (int64_t i = 0; i < (int64_t)num_steps * B; ++i) {
+      if (!std::isfinite(scales[i])) fail(SF_ERR_INVALID, "guidance scale %lld is not finite", (long long)i);
+      any = any || scales[i] != 1.0f;
+    }
+  const MultistepArgs ms{sigmas, table};
+  const GuidanceArgs ga{any ? scales : nullptr, any ? rescale : 0.0f, hist_io};
+  run_sampler(h, x, nullptr, ctx, emb, B, L0, num_steps, 1.0f, use_graph, ws, ws_bytes, stream, &ms, &ga);
   return SF_OK;
   SF_API_END
 }

@@ -303,12 +303,20 @@ class VSampler(nn.Module):
     ``"dpmpp_2m"`` are second-order multistep rules at one U-Net evaluation per step; additions, DESIGN.md "Multistep sampler"), and
     ``schedule`` any module whose ``forward(num_steps + 1, device=)`` returns finite, strictly decreasing sigmas inside [0, 1].
     ``forward(..., solver=, schedule=, sigmas=)`` override the constructor's choices for one call; ``sigmas`` are the ``num_steps + 1``
-    schedule values themselves."""
+    schedule values themselves.
+
+    Guidance schedules (additions, DESIGN.md "Guidance schedules"): ``embedding_scale`` may be a ``(B,)`` array or tensor, a ``(T,)`` or a
+    ``(T, B)`` array of scales; ``guidance_interval=(lo, hi)`` sets the scale to 1 at every step whose sigma lies outside, and steps whose
+    scales are all 1 skip the unconditional half of the batch; ``guidance_rescale`` in [0, 1] rescales each clip's guided direction towards
+    the level of the conditional one.  With a float scale, no interval and ``guidance_rescale == 0`` the call is what it was; otherwise
+    it runs as one ``sf_vsample_gx`` per run of guided / single-pass steps, and ``last_segments`` holds that plan."""
 
     diffusion_types = [VDiffusion]
 
-    def __init__(self, net: nn.Module, schedule: Optional[nn.Module] = None, use_graph: bool = True, solver: str = "ddim"):
+    def __init__(self, net: nn.Module, schedule: Optional[nn.Module] = None, use_graph: bool = True, solver: str = "ddim",
+                 guidance_rescale: float = 0.0, guidance_interval=None):
         super().__init__()
+        from .guidance import check_rescale
         from .solvers import SOLVERS
 
         if solver not in SOLVERS:
@@ -317,6 +325,9 @@ class VSampler(nn.Module):
         self.schedule = schedule if schedule is not None else LinearSchedule()
         self.use_graph = use_graph
         self.solver = solver
+        self.guidance_rescale = check_rescale(guidance_rescale)
+        self.guidance_interval = None if guidance_interval is None else (float(guidance_interval[0]), float(guidance_interval[1]))
+        self.last_segments = None   # the plan [(i0, i1, two)] of the last call that ran under a guidance schedule
 
     @property
     def net(self):
@@ -324,10 +335,12 @@ class VSampler(nn.Module):
 
     @torch.no_grad()
     def forward(self, x_noisy: Tensor, num_steps: int, show_progress: bool = False, *, embedding: Optional[Tensor] = None,
-                channels: Optional[Sequence[Tensor]] = None, embedding_scale: float = 1.0, solver: Optional[str] = None,
-                sigmas=None, schedule: Optional[nn.Module] = None, **kwargs) -> Tensor:
+                channels: Optional[Sequence[Tensor]] = None, embedding_scale=1.0, solver: Optional[str] = None,
+                sigmas=None, schedule: Optional[nn.Module] = None, guidance_rescale: Optional[float] = None, guidance_interval=None,
+                **kwargs) -> Tensor:
         if kwargs:
             raise TypeError(f"unsupported sampling arguments: {sorted(kwargs)}")
+        from . import guidance
         from .solvers import SOLVERS, check_sigmas, pack_table, solver_table
 
         solver = self.solver if solver is None else solver
@@ -336,8 +349,13 @@ class VSampler(nn.Module):
         if sigmas is not None and schedule is not None:
             raise ValueError("give `sigmas` or `schedule`, not both")
         schedule = self.schedule if schedule is None else schedule
+        phi = guidance.check_rescale(self.guidance_rescale if guidance_rescale is None else guidance_rescale)
+        guidance_interval = self.guidance_interval if guidance_interval is None else guidance_interval
+        scheduled = phi != 0.0 or guidance_interval is not None or not guidance.is_plain_scale(embedding_scale)
         assert embedding is not None, "ClassifierFreeGuidancePlugin requires embedding"
-        if sigmas is None and solver == "ddim" and _is_default_schedule(schedule):
+        if not scheduled:
+            self.last_segments = None
+        if not scheduled and sigmas is None and solver == "ddim" and _is_default_schedule(schedule):
             return self._net.engine().sample(x_noisy, num_steps, channels, embedding, embedding_scale, self.use_graph)
         if int(num_steps) < 1:
             raise ValueError(f"num_steps must be >= 1, got {num_steps}")
@@ -346,8 +364,12 @@ class VSampler(nn.Module):
         if isinstance(sigmas, Tensor):
             sigmas = sigmas.detach().to(device="cpu", dtype=torch.float32).numpy()
         sig = check_sigmas(sigmas, num_steps)
-        return self._net.engine().sample_ms(x_noisy, sig, pack_table(solver_table(sig, solver)), channels, embedding, embedding_scale,
-                                            self.use_graph)
+        table = pack_table(solver_table(sig, solver))
+        if not scheduled:
+            return self._net.engine().sample_ms(x_noisy, sig, table, channels, embedding, embedding_scale, self.use_graph)
+        scales = guidance.scale_table(embedding_scale, sig, x_noisy.shape[0], guidance_interval)
+        self.last_segments = guidance.plan_segments(scales)
+        return self._net.engine().sample_gx(x_noisy, sig, table, scales, self.last_segments, channels, embedding, phi, self.use_graph)
 
 
 def philox_normal(shape, seed: int, k: int, device, elem_offset: int = 0) -> Tensor:

@@ -33,9 +33,12 @@ Tensor = torch.Tensor
 def generate_batch(model, y: Tensor, z: Optional[Tensor] = None, text: Optional[Sequence[str]] = None, *,
                    num_steps: int = 150, length: int = 2 ** 18, embedding_scale: float = 7.5, cut_prefix: bool = False,
                    cond_text: bool = False, cut_length: Optional[int] = None, noise: Optional[Tensor] = None,
-                   generator: Optional[torch.Generator] = None, solver: Optional[str] = None, schedule=None) -> Tensor:
+                   generator: Optional[torch.Generator] = None, solver: Optional[str] = None, schedule=None,
+                   guidance_rescale: Optional[float] = None, guidance_interval=None) -> Tensor:
     """One batch of main/generation.py:69-89,100 on the device of ``model``.  Returns ``(B, 1, cut_length)``.
-    ``solver`` / ``schedule`` (additions): ``VSampler``'s solver name and schedule module for this call; ``None`` keeps the sampler's own."""
+    ``solver`` / ``schedule`` (additions): ``VSampler``'s solver name and schedule module for this call; ``None`` keeps the sampler's own.
+    ``embedding_scale`` may also be a ``(B,)``, ``(T,)`` or ``(T, B)`` array of scales, and ``guidance_rescale`` / ``guidance_interval``
+    are ``VSampler``'s (additions; DESIGN.md, "Guidance schedules"); ``None`` keeps the sampler's own."""
     device = model.device
     _lib.require_gpu_tensor(torch.empty(0, device=device), "generate_batch")
     B = y.shape[0]
@@ -48,16 +51,21 @@ def generate_batch(model, y: Tensor, z: Optional[Tensor] = None, text: Optional[
     else:
         z_latent = model.clap_encode_audio(z.to(device))                          # :75
     gen = model.model.sample(x_noisy=noise.to(device), num_steps=num_steps, channels=y_latent["xs"][2:-1],
-                             embedding=z_latent.to(device), embedding_scale=embedding_scale, **_solver_kwargs(solver, schedule))   # :77-83
+                             embedding=z_latent.to(device), embedding_scale=embedding_scale,
+                             **_solver_kwargs(solver, schedule, guidance_rescale, guidance_interval))   # :77-83
     if cut_prefix:
         # one device pass for the batch (:86-89, :100); IndexError on a track without onsets, as the reference's [0] does
         return cut_prefix_crop(gen, y[:, :1], cut_length or length)
     return gen[:, :, : (cut_length or length)]                                     # :91,100
 
 
-def _solver_kwargs(solver, schedule) -> dict:
-    """Only what the caller chose reaches ``sample()``: with neither, the call is what it was."""
+def _solver_kwargs(solver, schedule, guidance_rescale=None, guidance_interval=None) -> dict:
+    """Only what the caller chose reaches ``sample()``: with none of them, the call is what it was."""
     kw = {}
+    if guidance_rescale is not None:
+        kw["guidance_rescale"] = guidance_rescale
+    if guidance_interval is not None:
+        kw["guidance_interval"] = guidance_interval
     if solver is not None:
         kw["solver"] = solver
     if schedule is not None:
@@ -67,14 +75,16 @@ def _solver_kwargs(solver, schedule) -> dict:
 
 @torch.no_grad()
 def vary_batch(model, audio: Tensor, y: Tensor, z: Optional[Tensor] = None, text: Optional[Sequence[str]] = None, *, strength: float = 0.5,
-               num_steps: int = 50, embedding_scale: float = 7.5, cond_text: bool = False, seed: int = 0, solver: str = "ab2") -> Tensor:
+               num_steps: int = 50, embedding_scale: float = 7.5, cond_text: bool = False, seed: int = 0, solver: str = "ab2",
+               guidance_rescale: Optional[float] = None, guidance_interval=None) -> Tensor:
     """Variations of an existing clip ``audio`` ``(B, 1, L)`` under the onset track ``y`` and the CLAP conditioning: the clip is noised to
     the level ``strength`` in (0, 1],
 
         x_noisy = cos(strength * pi / 2) * audio + sin(strength * pi / 2) * philox_normal(audio.shape, seed, 0),
 
     and sampled from there on ``LinearSchedule(strength, 0)`` with ``solver``.  Small ``strength`` stays close to the clip, 1 forgets
-    it.  The noise is the device's counter-based generator: a pure function of ``seed``."""
+    it.  The noise is the device's counter-based generator: a pure function of ``seed``.  ``embedding_scale`` (a float or an array of
+    scales), ``guidance_rescale`` and ``guidance_interval`` are ``generate_batch``'s."""
     from .diffusion import LinearSchedule, philox_normal
 
     if not 0.0 < float(strength) <= 1.0:
@@ -88,7 +98,8 @@ def vary_batch(model, audio: Tensor, y: Tensor, z: Optional[Tensor] = None, text
     _, y_latent = model.onsets_encoder(y.to(device), with_info=True)
     z_latent = _embed(model, z, text, cond_text, device)
     return model.model.sample(x_noisy=x_noisy, num_steps=num_steps, channels=y_latent["xs"][2:-1], embedding=z_latent,
-                              embedding_scale=embedding_scale, solver=solver, schedule=LinearSchedule(float(strength), 0.0))
+                              embedding_scale=embedding_scale,
+                              **_solver_kwargs(solver, LinearSchedule(float(strength), 0.0), guidance_rescale, guidance_interval))
 
 
 def regions_to_keep_mask(regions, B: int, L: int) -> Tensor:
@@ -316,7 +327,7 @@ def generate_dataset(experiment_path: Union[str, Path], model, dataset: Iterable
                      num_steps: int = 150, length: int = 2 ** 18, embedding_scale: float = 7.5, cut_prefix: bool = False,
                      cond_text: bool = False, one_chunk_per_track: bool = False, cut_length: Optional[int] = None,
                      downsample_rate: Optional[int] = None, save_cond: bool = False, solver: Optional[str] = None,
-                     schedule=None) -> List[Path]:
+                     schedule=None, guidance_rescale: Optional[float] = None, guidance_interval=None) -> List[Path]:
     """Same signature as main/generation.py:12-30.  ``dataset``: the reference's un-batched chunk dataset (batched here with
     ``batch_size`` / ``num_workers`` + ``collate_fn``, :37-38) or an iterable of already-collated batches (``iter_batches``)."""
     experiment_path = Path(experiment_path)
@@ -336,7 +347,8 @@ def generate_dataset(experiment_path: Union[str, Path], model, dataset: Iterable
                 chunk_id += B
                 continue
         gen = generate_batch(model, y, z, text, num_steps=num_steps, length=length, embedding_scale=embedding_scale,
-                             cut_prefix=cut_prefix, cond_text=cond_text, cut_length=cut_length, solver=solver, schedule=schedule)
+                             cut_prefix=cut_prefix, cond_text=cond_text, cut_length=cut_length, solver=solver, schedule=schedule,
+                             guidance_rescale=guidance_rescale, guidance_interval=guidance_interval)
         out_sr = sample_rate
         cond = z.to(gen.device).to(torch.float32) if (save_cond and not cond_text) else None   # :93-96: the conditioning audio itself
         if downsample_rate:                                                       # :90-98, on the device instead of the CPU
